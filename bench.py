@@ -16,6 +16,9 @@ Extra objects on the JSON line: ``roofline`` (dominant kernel: the kNN distance/
 MFMA-bound), ``roofline_cheby`` (the HBM-bound CSR recurrence the north star's 70 % target refers
 to), ``cpu_baseline`` (the oracle -- an in-repo scipy/sklearn restatement of the reference path --
 timed on a bounded sample on this box's host cores), ``stages`` (per-stage seconds of one step).
+
+``--dump-outputs DIR`` writes the densities the last timed step returned to DIR (``dump_outputs``); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -219,6 +222,29 @@ def cheby_roofline(G, ev, order, p, N, d):
     }
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, dens, limit=DUMP_LIMIT_BYTES):
+    """What the timed path handed its caller in the last timed step -- the [N, p] densities of ``fit_transform``, a DataFrame with
+    one column per sample label -- written as ``dirname/densities.npy`` (float64, columns in the DataFrame's order), so that two
+    builds run with the same arguments can be compared output for output.  Above ``limit`` bytes a fixed, seeded sample of rows
+    is written instead, with its row numbers (as float64) in ``densities_rows.npy``; the two files together stay within ``limit``.
+    Returns {file name: shape}."""
+    os.makedirs(dirname, exist_ok=True)
+    vals = np.ascontiguousarray(dens.to_numpy(dtype=np.float64))
+    files = {}
+    if vals.nbytes > limit:
+        keep = limit // (8 * vals.shape[1] + 8)
+        rows = np.sort(np.random.default_rng(0).choice(vals.shape[0], size=keep, replace=False))
+        vals = np.ascontiguousarray(vals[rows])
+        np.save(os.path.join(dirname, "densities_rows.npy"), rows.astype(np.float64))
+        files["densities_rows.npy"] = list(rows.shape)
+    np.save(os.path.join(dirname, "densities.npy"), vals)
+    files["densities.npy"] = list(vals.shape)
+    return files
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -241,6 +267,9 @@ def main():
     ap.add_argument("--vfc", action="store_true", help="also time VertexFrequencyCluster (filter-bank method) on the benchmark graph "
                                                        "(BASELINE configs[4] on one GPU) and report `vfc` / `roofline_vfc`")
     ap.add_argument("--force-sharded", action="store_true", help="use the row-sharded driver even with one rank (testing)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the densities the last timed step returned as DIR/densities.npy (float64, "
+                         "[cells, labels]; a fixed, seeded sample of rows when they exceed 64 MB)")
     args = ap.parse_args()
 
     import torch
@@ -308,6 +337,10 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     gc.enable()
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # (outside the timed region; every rank holds the whole [N, p] frame, rank 0 writes it)
+        dumped = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, dens), "columns": [str(c) for c in dens.columns]}
     ev = mgraph.event_times_ms()
     mgraph.record_events(False)
     # the same step with X handed over as a HOST array (SURVEY 8d counts the H2D copy; `value` does not -- the bench contract
@@ -383,6 +416,8 @@ def main():
             "lanczos_iterations": int(G.lmax_info.get("iterations", 0)),
         },
     }
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if per_rank is not None:
         # per Chebyshev step every rank all-gathers the iterate (8 p bytes per cell), per Lanczos iteration the iterate (8 bytes per
         # cell) and 3 x 64 doubles; the symmetrisation is one fixed-capacity all-to-all

@@ -142,6 +142,32 @@ def test_bench_workload_generator_is_the_oracles():
         assert np.array_equal(Xa, Xb) and np.array_equal(la, lb)
 
 
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: the densities as float64 .npy in the frame's column order; above the size limit a seeded sample
+    of rows, the same one every run, with its row numbers beside it and both files within the limit."""
+    import importlib.util
+    import os
+
+    spec = importlib.util.spec_from_file_location("bench_module", os.path.join(os.path.dirname(os.path.dirname(__file__)), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(1)
+    dens = pd.DataFrame(rng.random((1000, 2)), columns=["ctrl", "expt"])
+    assert bench.dump_outputs(str(tmp_path / "full"), dens) == {"densities.npy": [1000, 2]}
+    full = np.load(tmp_path / "full" / "densities.npy")
+    assert full.dtype == np.float64 and np.array_equal(full, dens.values)
+    limit = 4800
+    files = bench.dump_outputs(str(tmp_path / "a"), dens, limit=limit)
+    bench.dump_outputs(str(tmp_path / "b"), dens, limit=limit)
+    assert files == {"densities_rows.npy": [200], "densities.npy": [200, 2]}
+    rows = np.load(tmp_path / "a" / "densities_rows.npy")
+    part = np.load(tmp_path / "a" / "densities.npy")
+    assert rows.dtype == np.float64 and part.dtype == np.float64 and rows.nbytes + part.nbytes <= limit
+    assert np.array_equal(rows, np.load(tmp_path / "b" / "densities_rows.npy")) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(part, dens.values[rows.astype(np.int64)])
+    assert np.array_equal(part, np.load(tmp_path / "b" / "densities.npy"))
+
+
 def test_vertex_frequency_cluster_argument_checks():
     """Same checks and messages as reference meld/cluster.py (test/test_meld.py:296-345); they all fire
     before any device work."""
