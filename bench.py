@@ -12,10 +12,16 @@ Workload: BASELINE.json's metric is quoted at 1M cells x 50 dims (configs[3]); i
 N=1 runs exactly that.  With --gpus N > 1 the cells are row-sharded over the ranks (strong scaling:
 the problem size stays 1M cells).
 
-Extra objects on the JSON line: ``roofline`` (dominant kernel: the kNN distance/top-k kernel,
-MFMA-bound), ``roofline_cheby`` (the HBM-bound CSR recurrence the north star's 70 % target refers
-to), ``cpu_baseline`` (the oracle -- an in-repo scipy/sklearn restatement of the reference path --
-timed on a bounded sample on this box's host cores), ``stages`` (per-stage seconds of one step).
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, ``--dump-outputs``
+and the result line.  Its extra objects come from the HIP events of the timed steps themselves:
+``roofline`` (dominant kernel: the kNN distance/top-k kernel, MFMA-bound), ``roofline_filter`` and
+``roofline_cheby`` (the HBM-bound CSR recurrence the north star's 70 % target refers to).
+
+``--full`` adds what takes runs of its own: ``value_host_input`` (the same steps with X on the host),
+``roofline_cheby_c3`` / ``roofline_d100`` / ``roofline.unpruned`` (untimed passes at other sizes and
+configurations) and ``cpu_baseline`` (the oracle -- an in-repo scipy/sklearn restatement of the
+reference path -- timed on a bounded sample on the host cores).  ``--stages`` (per-stage seconds of
+one step) and ``--vfc`` are separate opt-ins, as before.
 
 ``--dump-outputs DIR`` writes the densities the last timed step returned to DIR (``dump_outputs``); the inputs are seeded,
 so two builds run with the same arguments can be compared output for output.
@@ -255,15 +261,19 @@ def main():
     ap.add_argument("--knn", type=int, default=15)
     ap.add_argument("--beta", type=float, default=60)
     ap.add_argument("--order", type=int, default=30)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure what takes runs of its own: the steps with X on the host, the extra "
+                         "untimed passes of the 1M run and the CPU baseline (each can be skipped by the options below)")
     ap.add_argument("--cpu-sample", type=int, default=50000,
-                    help="largest CPU-baseline sample (0 = skip); also run at 1/2 and 1/4 of it.  Default 50000: 12.5k / 25k / "
-                         "50k cells, about 45 s of host time (the line also carries the round's recorded run of SURVEY 8d's "
-                         "own 50k / 100k / 200k, which takes 27 minutes: --cpu-full)")
-    ap.add_argument("--cpu-full", action="store_true", help="time SURVEY 8d's 50k / 100k / 200k samples (27 minutes of host time)")
-    ap.add_argument("--no-host-input", action="store_true", help="skip the extra untimed-region passes with X on the host")
+                    help="with --full: largest CPU-baseline sample (0 = skip); also run at 1/2 and 1/4 of it.  Default 50000: "
+                         "12.5k / 25k / 50k cells, about 45 s of host time (the line also carries the round's recorded run of "
+                         "SURVEY 8d's own 50k / 100k / 200k, which takes 27 minutes: --cpu-full)")
+    ap.add_argument("--cpu-full", action="store_true", help="with --full: time SURVEY 8d's 50k / 100k / 200k samples (27 minutes of "
+                                                            "host time)")
+    ap.add_argument("--no-host-input", action="store_true", help="with --full: skip the extra untimed-region passes with X on the host")
     ap.add_argument("--stages", action="store_true", help="extra untimed step with per-stage host timers")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra untimed passes of the default 1M run (C3's recurrence "
-                                                            "roofline at 500k cells, the unpruned search)")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra untimed passes of the 1M run (C3's recurrence "
+                                                            "roofline at 500k cells, 1M x 100, the unpruned search)")
     ap.add_argument("--vfc", action="store_true", help="also time VertexFrequencyCluster (filter-bank method) on the benchmark graph "
                                                        "(BASELINE configs[4] on one GPU) and report `vfc` / `roofline_vfc`")
     ap.add_argument("--force-sharded", action="store_true", help="use the row-sharded driver even with one rank (testing)")
@@ -271,6 +281,8 @@ def main():
                     help="after the timed steps, write the densities the last timed step returned as DIR/densities.npy (float64, "
                          "[cells, labels]; a fixed, seeded sample of rows when they exceed 64 MB)")
     args = ap.parse_args()
+    if args.cpu_full and not args.full:
+        ap.error("--cpu-full times the CPU baseline, which runs with --full only")
 
     import torch
 
@@ -343,11 +355,11 @@ def main():
         dumped = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, dens), "columns": [str(c) for c in dens.columns]}
     ev = mgraph.event_times_ms()
     mgraph.record_events(False)
-    # the same step with X handed over as a HOST array (SURVEY 8d counts the H2D copy; `value` does not -- the bench contract
-    # starts with the inputs resident): the SAME protocol as `value` -- one warm-up, then args.steps steps in one
+    # --full: the same step with X handed over as a HOST array (SURVEY 8d counts the H2D copy; `value` does not -- the bench
+    # contract starts with the inputs resident): the SAME protocol as `value` -- one warm-up, then args.steps steps in one
     # synchronize-bracketed region
     host_ms, host_elapsed = [], None
-    if world == 1 and not args.no_host_input:
+    if args.full and world == 1 and not args.no_host_input:
         X_host = X.cpu().numpy()
         meld_amd.MELD(knn=args.knn, beta=args.beta, chebyshev_order=args.order, verbose=0).fit_transform(X_host, labels)
         gc.collect()
@@ -400,8 +412,8 @@ def main():
         "data": "synthetic",
         "config": {
             "workload": "{} cells x {} dims ({}), 20-cluster 10-d latent mixture, seed 0; `value`: X resident in HBM (fp64) "
-            "when the timed region starts (`value_host_input`: the same step with X handed over as a host array, SURVEY "
-            "8d's host-visible definition), labels host strings, densities back as a host DataFrame; "
+            "when the timed region starts (`value_host_input`, with --full: the same step with X handed over as a host array, "
+            "SURVEY 8d's host-visible definition), labels host strings, densities back as a host DataFrame; "
             "knn={}, decay=40, thresh=1e-4, anisotropy=1, beta={}, heat filter, chebyshev_order={}, p={} labels".format(
                 N, d, {1_000_000: "BASELINE configs[3] size, the size the metric is quoted on", 500_000: "BASELINE configs[2]",
                        50_000: "BASELINE configs[1]"}.get(N, "custom size"), args.knn, args.beta, args.order, p),
@@ -522,7 +534,7 @@ def main():
         out["roofline"]["frac_filter_plus_search"] = (ex_f + out["roofline"]["achieved"] * 1e12 * float(np.mean(ev["knn_topk"])) * 1e-3) / t_both / 1e12 / PEAK_MFMA_F16_TFLOPS
     if "cheby_steps" in ev:
         out["roofline_cheby"] = cheby_roofline(G, ev, args.order, p, N, d)
-    if world == 1 and not args.no_extra and N == 1_000_000 and d == 50:
+    if args.full and world == 1 and not args.no_extra and N == 1_000_000 and d == 50:
         # BASELINE configs[2] (C3, 500k x 50) is the configuration the north star's 70 % recurrence target is quoted on: one extra
         # untimed pass at that size (a warm-up + two steps), its recurrence launches timed by the same HIP events
         Xc, lc = synthetic_cells(500_000, n_dims=d, seed=0)
@@ -655,7 +667,7 @@ def main():
                 "ms_per_spmm": 1e3 * t_sp, "ms_per_spmm_mean": float(np.mean(ev2["vfc_spmm"])), "spmms": len(ev2["vfc_spmm"]), "traffic": None,
             }
     out["value_definition"] = ("X resident in HBM when the timed region starts (the bench contract: inputs resident, the PCIe-inclusive "
-                               "rate is reported beside it as `value_host_input` and is SURVEY 8d's host-visible figure)")
+                               "rate is reported beside it by --full as `value_host_input` and is SURVEY 8d's host-visible figure)")
     if host_ms:
         # SURVEY 8d's metric counts the H2D copy of X: this is the figure to compare with it (`value` starts X-resident)
         out["value_host_input"] = N * len(host_ms) / host_elapsed
@@ -669,7 +681,7 @@ def main():
             "synchronize-bracketed region after one warm-up -- the protocol of `value`; SURVEY 8d's host-visible definition, "
             "reported beside `value`, which starts with X resident as the bench contract prescribes".format(N * d * 8 / 1e6, len(host_ms)),
         }
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         out["cpu_baseline"] = cpu_baseline(args.cpu_sample, d, args.knn, args.beta, args.order, N, full_protocol=args.cpu_full)
         out["cpu_baseline"]["chebyshev_at_full_size"] = cpu_chebyshev_full_size(G, labels, args.beta, args.order)
         ch = out["cpu_baseline"]["chebyshev_at_full_size"]

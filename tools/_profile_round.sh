@@ -11,7 +11,7 @@ stamp() { echo "# commit $commit, $(date -u +%Y-%m-%dT%H:%MZ), $(rocminfo 2>/dev
 cpu=""; [ "$quick" = "cpufull" ] && cpu="--cpu-full"   # (the 27-minute CPU protocol only when asked for)
 for n in 1000000 500000; do
   c=$cpu; [ $n != 1000000 ] && c="--cpu-sample 0"
-  python bench.py --cells $n $c 2>$out/bench_$n.err > $out/bench_$n.json
+  python bench.py --full --cells $n $c 2>$out/bench_$n.err > $out/bench_$n.json
   python - $out/bench_$n.json $commit <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); d["commit"] = sys.argv[2]

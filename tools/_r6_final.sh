@@ -5,7 +5,7 @@ commit=${1:-unknown}; out=gpurun_out/final_r06; mkdir -p $out; export TMPDIR=/tm
 stamp() { echo "# commit $commit, $(date -u +%Y-%m-%dT%H:%MZ)"; }
 timeout 2700 python -m pytest tests -x -q -m gpu 2>&1 | tail -3 > $out/gpu_tests.txt; cat $out/gpu_tests.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -1
-env -u MELD_DEV python bench.py 2>$out/bench.err > $out/bench_1M.json; python - $out/bench_1M.json $commit <<'PY'
+env -u MELD_DEV python bench.py --full 2>$out/bench.err > $out/bench_1M.json; python - $out/bench_1M.json $commit <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); d["commit"] = sys.argv[2]
 open(sys.argv[1], "w").write(json.dumps(d) + "\n")
