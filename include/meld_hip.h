@@ -655,6 +655,33 @@ int meld_scatter_rows_f64(const double* in, const int64_t* perm, int64_t n_rows,
 /* out[i,:] = in[i,:] / sum_j |in[i,j]|  (rows of zeros are copied unchanged, as sklearn does) */
 int meld_normalize_rows_l1(const double* in, double* out, int64_t n_rows, int p, meld_stream_t stream);
 
+/* ---- sparse input: truncated SVD of a cell-by-gene CSR matrix (csr_dense.hip; replaces [UPSTREAM graphtools
+ *      Data._reduce_data -> sklearn TruncatedSVD] on scipy.sparse input, reached from meld/meld.py:273) --------------------
+ * The CSR operand: rowptr[n_rows + 1] int64 (rowptr[0] = 0), col[nnz] int32, val[nnz] fp32 (val_f32 = 1, widened in the
+ * kernel) or fp64; columns of a row need not be sorted, but the summation order is their storage order.
+ *
+ * meld_csr_spmm_f64: Y[i][0:r] = sum_j val[j] B[col[j]][0:r] for every row i, B[*][ldb] and Y[n_rows][ldy] row-major fp64.
+ *   The sum runs in fp64 in storage order inside a segment of MELD_CSR_SEG entries of a row; a row of more entries is
+ *   split into segments whose partial sums (partial[part_off[i] + s][r]) are added in segment order by a second pass.
+ *   No atomics: the result is a function of the operands alone.  The work plan (built by the caller from rowptr):
+ *     unit_row[n_units]: the row of each unit (a unit = one segment; max(1, ceil(len / MELD_CSR_SEG)) units per row,
+ *                        consecutive, in segment order); unit_off[n_rows]: the first unit of each row;
+ *     part_off[n_rows]: the first partial slot of each row of more than one segment; split_rows[n_split_rows]: those rows.
+ *   Every col[j] must be < the number of rows of B (checked by the caller). */
+#define MELD_CSR_SEG 1024
+int meld_csr_seg_length(void);
+int meld_csr_spmm_f64(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t n_rows,
+                      const int32_t* unit_row, const int64_t* unit_off, int64_t n_units, const int64_t* part_off,
+                      const int32_t* split_rows, int64_t n_split_rows, double* partial, const double* B, int64_t ldb,
+                      int r, double* Y, int64_t ldy, meld_stream_t stream);
+/* keys[j] = col[j] << 32 | row of entry j, vals[j] = val[j] as fp64: sorted by meld_sort_pairs_u64_f64 and assembled by
+ * meld_csr_from_keys they are the CSR of the transpose, rows ascending inside each column (n_rows < 2^31). */
+int meld_csr_transpose_keys(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t n_rows,
+                            uint64_t* keys, double* vals, meld_stream_t stream);
+/* out[i][0:n_cols] (row stride ldo) = row row_begin + i of the CSR matrix, zeros elsewhere, i < n_rows (no duplicate columns) */
+int meld_csr_rows_to_dense_f64(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t row_begin,
+                               int64_t n_rows, int64_t n_cols, double* out, int64_t ldo, meld_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -88,6 +88,10 @@ SIGNATURES = {
     "meld_merge_temp_bytes": (_sz, [_i64]),
     "meld_coo_merge": (_i32, [_ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
     "meld_csr_from_keys": (_i32, [_ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr]),
+    "meld_csr_seg_length": (_i32, []),
+    "meld_csr_spmm_f64": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _ptr, _ptr, _i64, _i32, _ptr, _i64, _ptr]),
+    "meld_csr_transpose_keys": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _ptr, _ptr, _ptr]),
+    "meld_csr_rows_to_dense_f64": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _i64, _ptr, _i64, _ptr]),
     "meld_csr_bucket_slots": (_i32, []),
     "meld_coo_scatter_rows": (_i32, [_ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr]),
     "meld_coo_emit_scatter": (_i32, [_i64, _ptr, _ptr, _i32, _i32, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),

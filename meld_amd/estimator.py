@@ -64,6 +64,14 @@ _GRAPH_PARAMS = ("knn", "decay", "n_pca", "thresh", "distance", "anisotropy", "n
 _PASSIVE_PARAMS = ("n_jobs", "random_state", "verbose")
 
 
+def _same_csr(old, A):
+    """Refit detection of sparse input: the same shape, the same number of entries and equal indptr / indices / data."""
+    from scipy import sparse
+
+    return (sparse.issparse(old) and old.format == "csr" and old.shape == A.shape and old.nnz == A.nnz
+            and np.array_equal(old.indptr, A.indptr) and np.array_equal(old.indices, A.indices) and np.array_equal(old.data, A.data))
+
+
 class GraphEstimator(object):
     """Estimator that owns a graph built from data."""
 
@@ -179,6 +187,18 @@ class GraphEstimator(object):
             if self.graph is None:
                 self._log("Building graph on {} samples and {} features.".format(X.shape[0], X.shape[1]))
                 self.graph = self._build_timed(X, **kwargs)
+            return self
+        from . import sparse as _sparse
+
+        if _sparse.is_sparse_input(X):
+            # sparse cell-by-gene input: one canonical CSR matrix on the host, never densified there (meld_amd/sparse.py)
+            A = _sparse.to_host_csr(X)
+            if self.X is not None and not _same_csr(self.X, A):
+                self.graph = None
+            self.X = A
+            if self.graph is None:
+                self._log("Building graph on {} samples and {} features.".format(A.shape[0], A.shape[1]))
+                self.graph = self._build_timed(A, **kwargs)
             return self
         if hasattr(X, "X") and not isinstance(X, np.ndarray):  # AnnData-like
             X = X.X

@@ -145,6 +145,21 @@ class MELD(GraphEstimator):
             raise NotImplementedError("kernel_symm other than '+' with sample_idx (MNN graph) is not implemented")
         if not torch.cuda.is_available():
             raise RuntimeError("meld_amd needs a ROCm GPU (MI355X); there is no CPU fallback")
+        from . import sparse as _sparse
+
+        svd_scores = None
+        if _sparse.is_sparse_input(data):
+            # sparse input (meld_amd/sparse.py): graphtools reduces it with an UNCENTRED truncated SVD where it reduces at all
+            # (Data._reduce_data); without a reduction, and for precomputed matrices, it is densified on the device and takes
+            # the dense path below
+            A = _sparse.DeviceCSR.from_input(data)
+            if (self.n_pca is not None and self.n_pca < min(A.shape)) and not str(self.distance).lower().startswith("precomputed"):
+                self._log("Calculating truncated SVD ({} components)...".format(self.n_pca))
+                svd_scores = _sparse.truncated_svd_project(A, self.n_pca, seed=42 if self.random_state is None else int(self.random_state))
+                data = svd_scores
+            else:
+                data = A.to_dense()
+            del A
         if isinstance(data, torch.Tensor):
             X = data.to(device="cuda", dtype=torch.float64)
         else:
@@ -165,7 +180,7 @@ class MELD(GraphEstimator):
             finite = bool(torch.isfinite(X.sum(dim=0)).all())
         if not finite and not bool(torch.isfinite(X).all()):
             raise ValueError("Input data contains NaN or infinity")
-        self.data_nu = None
+        self.data_nu = svd_scores
         if str(self.distance).lower().startswith("precomputed"):
             # [UPSTREAM graphtools GraphEstimator._parse_input]: the input IS a square matrix of pairwise distances or
             # affinities ("precomputed": told apart by its first diagonal entry, 0 = distances); no PCA, dense graph
@@ -179,7 +194,7 @@ class MELD(GraphEstimator):
             if not kind:
                 kind = "distance" if float(X[0, 0]) == 0.0 else "affinity"
             return build_precomputed_graph(X, kind, knn=self.knn, decay=self.decay, thresh=self.thresh, anisotropy=self.anisotropy, symm=symm)
-        if self.n_pca is not None and self.n_pca < min(tuple(X.shape)):
+        if svd_scores is None and self.n_pca is not None and self.n_pca < min(tuple(X.shape)):
             # graphtools reduces the data with PCA first (Data._reduce_data) and builds the graph on
             # the scores; here: exact top-n_pca subspace on the device (meld_amd/pca.py)
             from .pca import pca_project
