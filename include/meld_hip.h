@@ -134,7 +134,7 @@ int meld_knn16_prepare_scaled(const double* X, int64_t N, int d, const double* m
  * index of query 0 (the scan of every workgroup starts at its own position among the references and
  * wraps around).
  * thr_seed (optional, q_count floats, scaled units) = the thr_init the search of the same queries will be
- * started with (meld_knn16_seed_thresholds*), nprod = that search's products: thresholds only fall, so a tile
+ * started with (meld_knn16_seed_thresholds_mfma), nprod = that search's products: thresholds only fall, so a tile
  * that no query of the wave can reach from its OWN start threshold (|p - c_t| - rho_t > sqrt(seed_p + E) for
  * all 64 cells p) is marked +inf in the table.  The table is then valid only for a search started from
  * exactly these thresholds (or lower ones).
@@ -187,15 +187,12 @@ int meld_knn16_research_thresholds(const int32_t* rows, int64_t n_rows, int64_t 
  * own workgroups into its own candidate rows (buffers of n_slices * roundup(q_count, BQ) rows);
  * meld_knn16_merge_slices then writes the ksel smallest of the union to the final rows. */
 /* Start values for the thresholds of meld_knn16_topk's first pass (thr_init, scaled units, roundup(q_count, BQ)
- * floats): the (knn+1)-th smallest distance of a query within its own block of BQ cells bounds its bandwidth from
- * above, so nothing beyond radius_factor^2 times that (plus the error allowance) can be wanted.  Spares the scan the
- * wholesale appends of its first tiles.  q_begin must be a multiple of BQ.  No reference counterpart. */
-int meld_knn16_seed_thresholds(const double* X, int64_t N, int d, const double* mean, const float* scale_info,
-                               const float* norm2_max, int64_t q_begin, int64_t q_count, int knn, double radius_factor,
-                               int nprod, float* thr_init, meld_stream_t stream);
-/* The same start values from the fp16 operands of meld_knn16_prepare, computed on the matrix pipe over the query
- * block's own tiles and side_tiles on either side in index order (side_tiles <= 0: n_ref / 12500, between 8 and 64 --
- * the cost grows with N, what tighter seeds save in the search and through meld_knn16_bounds' per-query test with N^2). */
+ * floats) from the fp16 operands of meld_knn16_prepare, computed on the matrix pipe: the (knn+1)-th smallest distance of
+ * a query among the cells of its block's own tiles and side_tiles on either side in index order (side_tiles <= 0:
+ * n_ref / 12500, between 8 and 64 -- the cost grows with N, what tighter seeds save in the search and through
+ * meld_knn16_bounds' per-query test with N^2) bounds its bandwidth from above, so nothing beyond radius_factor^2 times
+ * that (plus the error allowance) can be wanted.  Spares the scan the wholesale appends of its first tiles.  q_begin
+ * must be a multiple of BQ; knn + 1 > 64: every row +inf.  No reference counterpart. */
 int meld_knn16_seed_thresholds_mfma(const void* Q16, const float* Qn, const void* Rt16, const float* scale_info,
                                     const float* norm2_max, int64_t n_ref, int d, int64_t q_begin, int64_t q_count,
                                     int knn, double radius_factor, int nprod, int side_tiles, float* thr_init,
@@ -216,7 +213,7 @@ int meld_knn16_block_work(const void* lb2, const float* thr_seed, int64_t n_ref,
                           const float* norm2_max, const float* scale_info, int32_t* work, meld_stream_t stream);
 /* Step lists of the first pass (replaces the per-step use of the pruning table inside the search; graphtools
  * build_kernel_to_data's kNN query reached from /root/reference/meld/meld.py:273 has no counterpart -- this is how the
- * brute-force scan is cut down).  With start thresholds from meld_knn16_seed_thresholds* the tiles a query block can rule out
+ * brute-force scan is cut down).  With start thresholds from meld_knn16_seed_thresholds_mfma the tiles a query block can rule out
  * are known before the search (what the falling thresholds add is 1.5 % of the blocks at 1M cells), so they are written
  * down once: list[b * list_stride + i] = tile | (bit w set: wave w of block b cannot rule the tile out) << 24 for the
  * i-th step of block b in scan order, cnt[b] = its steps (>= 1), which is also the block's work for block_order.

@@ -1972,89 +1972,17 @@ __global__ __launch_bounds__(256) void prepare16_kernel(const double* __restrict
 
 // Threshold seeds.  The scan starts with every threshold at +inf, so the first tiles of a workgroup -- its own
 // 256 cells -- are appended wholesale (256 appends and ~3 compactions per row, a third of what learning the
-// thresholds costs the search).  A valid start value is cheap: the (knn+1)-th smallest distance of a cell *within its
-// own block of 256* (self included) bounds its bandwidth from above, hence
-//     thr_init = rf^2 (A (1 + 1e-5) + 2^-20 n_max) + 1.01 E_row
-// bounds the approximate d2 of every reference the kernel radius can reach (A is computed here by direct fp32
-// differences of the same centred, scaled coordinates the search uses: relative error ~3e-6 plus the fp32 rounding of
-// the inputs, 2^-21 n_max).  One workgroup per block: the 256 cells in LDS, thread i scans them keeping its knn+1
-// smallest values in registers.
+// thresholds costs the search).  A valid start value is cheap: the (knn+1)-th smallest distance of a cell among the cells
+// of its own and nearby tiles (self included) bounds its bandwidth from above.
 constexpr int SEED_KMAX = 64;  // largest knn + 1 a register list holds (longer: no seed)
-// (rows are zero-padded to SEED_D coordinates -- 60 / 104 / 144: 60 / 104 / 144 KiB of dynamic LDS -- and read as
-// broadcast float4, the thread's own row once into registers)
-template <int SEED_K, int SEED_D>  // register list length >= knn + 1; padded dimension >= d
-__global__ __launch_bounds__(256) void knn16_seed_kernel(const double* __restrict__ X, int64_t N, int d,
-                                                         const double* __restrict__ mean,
-                                                         const float* __restrict__ scale_info,
-                                                         const float* __restrict__ norm2_max, int64_t q_begin,
-                                                         int64_t q_count, int knn1, float rf2, float err_c, float err_l,
-                                                         float* __restrict__ thr_init) {
-  extern __shared__ __attribute__((aligned(16))) float xs[];  // [256][SEED_D]: rows zero-padded to SEED_D coordinates
-  const int tid = threadIdx.x;
-  constexpr int ldx = SEED_D;
-  const int64_t row0 = q_begin + (int64_t)blockIdx.x * K16_BQ;
-  const int n_here = (int)max((int64_t)0, min((int64_t)K16_BQ, q_begin + q_count - row0));
-  const float s = scale_info[0];
-  for (int u = tid; u < K16_BQ * SEED_D; u += 256) xs[u] = 0.0f;
-  __syncthreads();
-  for (int u = tid; u < K16_BQ * d; u += 256) {
-    const int r = u / d, k = u - r * d;
-    if (r < n_here) xs[r * ldx + k] = s * (float)(X[(row0 + r) * d + k] - mean[k]);
-  }
-  __syncthreads();
-  // the SEED_K smallest values seen so far, ascending; inserting v and dropping the largest is one median per slot:
-  // new[e] = med3(old[e - 1], v, old[e])
-  float best[SEED_K];
-#pragma unroll
-  for (int e = 0; e < SEED_K; ++e) best[e] = INFINITY;
-  // own row in registers (padded coordinates are zero on both sides and add nothing)
-  float xr[SEED_D];
-#pragma unroll
-  for (int k = 0; k < SEED_D; ++k) xr[k] = xs[tid * ldx + k];
-  float nq = 0.0f;
-#pragma unroll
-  for (int k = 0; k < SEED_D; ++k) nq = fmaf(xr[k], xr[k], nq);
-  for (int j = 0; j < n_here; ++j) {
-    const float4* xj = reinterpret_cast<const float4*>(xs + j * ldx);  // (same address in every lane: LDS broadcast)
-    float acc0 = 0.0f, acc1 = 0.0f;
-#pragma unroll
-    for (int k4 = 0; k4 < SEED_D / 4; ++k4) {
-      const float4 c = xj[k4];
-      const float t0 = xr[4 * k4] - c.x, t1 = xr[4 * k4 + 1] - c.y, t2 = xr[4 * k4 + 2] - c.z, t3 = xr[4 * k4 + 3] - c.w;
-      acc0 = fmaf(t0, t0, acc0);
-      acc1 = fmaf(t1, t1, acc1);
-      acc0 = fmaf(t2, t2, acc0);
-      acc1 = fmaf(t3, t3, acc1);
-    }
-    const float acc = acc0 + acc1;
-    if (acc < best[SEED_K - 1]) {
-#pragma unroll
-      for (int e = SEED_K - 1; e > 0; --e) best[e] = __builtin_amdgcn_fmed3f(best[e - 1], acc, best[e]);
-      best[0] = fminf(best[0], acc);
-    }
-  }
-  float worst = INFINITY;  // the knn1-th smallest
-#pragma unroll
-  for (int e = 0; e < SEED_K; ++e)
-    if (e == knn1 - 1) worst = best[e];
-  if (tid < K16_BQ) {
-    float out = INFINITY;
-    if (tid < n_here && n_here >= knn1 && worst < INFINITY) {
-      const float nmax_s = norm2_max[0] * s * s;
-      const float e_row = (err_c * nmax_s + err_l * sqrtf(nq * nmax_s)) * 1.01f;
-      out = (rf2 * (worst * 1.00001f + 9.5367431640625e-07f * nmax_s) + e_row) * 1.000001f + 1e-30f;
-    }
-    thr_init[(int64_t)blockIdx.x * K16_BQ + tid] = out;
-  }
-}
 
-// The same seeds from a wider neighbourhood on the matrix pipe: a workgroup takes its 256 queries (B fragments, as in
+// The seeds on the matrix pipe: a workgroup takes its 256 queries (B fragments, as in
 // the search) against its own four reference tiles and the four on either side in index order (768 cells: in locality
 // order the next leaves along the chain) -- 192 MFMAs per wave -- and every lane keeps the SEED_K smallest approximate
 // d2 of its two queries sorted in registers (one v_med3 per slot and insertion); the two half-lanes of a query then
 // merge their lists.  The approximate distance may fall short of the exact one by the row's search-error allowance, so
 //     thr_init = rf^2 (A~ + 1.01 E_row + 2^-20 n_max) + 1.01 E_row.
-// More cells than the fp32 kernel above looks at (768 vs 256: a tighter bound) for a tenth of its time.
+// (An earlier fp32 kernel over the own block only looked at 256 cells, at ten times the cost.)
 // `side` = tiles on either side of the workgroup's own K16_BQ / K16_TS tiles.  Tighter seeds pay twice since the pruning
 // table tests every query against its own seed (meld_knn16_bounds): at 1M x 50, side 4 / 16 / 32 / 64 cost 0.6 / 1.2 /
 // 1.9 / 3.3 ms and leave the search at 45.9 / 41.9 / 40.9 / 38.9 ms.  The cost grows with N, the gain with N^2: the
@@ -2504,7 +2432,7 @@ static int k16_bounds_impl(const double* X, int64_t N, int d, const double* mean
   const float ec = (float)meld_knn16_error_coef(1, d);
   const float es = (float)meld_knn16_error_coef(nprod, d);  // the search's allowance: a tile is skipped only if d2_approx < thr fails for sure
   // queries = all the cells: wave w is tile w and the table can be symmetrised (see knn16_bounds_symmetrize_kernel)
-  const bool symmetric = q_begin == 0 && q_count == N && meld_dev_getenv("MELD_KNN_SYMMETRIC_BOUNDS_OFF") == nullptr;
+  const bool symmetric = q_begin == 0 && q_count == N;
 #define K16_BOUNDS_LAUNCH(KBV, SD, BTV)                                                                                   \
   hipLaunchKernelGGL((knn16_tile_bounds_kernel<KBV, SD, BTV>), dim3(gx, gy), dim3(BTV), 0, st, c16, cn, cr,               \
                      reinterpret_cast<const _Float16*>(Rt16), n_t, (int)(q_begin / K16_TS), n_q, ec, norm2_max,           \
@@ -2714,11 +2642,6 @@ __global__ __launch_bounds__(256) void knn16_step_list_bits_kernel(const unsigne
   if (tid == 0) cnt[bx] = base;
 }
 
-static int k16_two_sided() {  // scan order: own tiles, then alternately forwards / backwards (0 = forwards only; profiling hook)
-  const char* e = meld_dev_getenv("MELD_KNN16_TWO_SIDED");
-  return e ? (atoi(e) != 0) : 1;
-}
-
 extern "C" int meld_knn16_step_lists(const void* lb2, const float* thr_seed, int64_t n_ref, int d, int64_t q_count, int nprod,
                                      const float* norm2_max, const float* scale_info, int64_t q_begin, uint32_t* list,
                                      int64_t list_stride, int32_t* cnt, meld_stream_t stream) {
@@ -2730,7 +2653,7 @@ extern "C" int meld_knn16_step_lists(const void* lb2, const float* thr_seed, int
   const int tile_origin = (int)((q_begin / K16_TS) % n_tiles);
   hipLaunchKernelGGL(knn16_step_list_kernel, dim3((unsigned)ceil_div(q_count, K16_BQ)), dim3(256), 0, S(stream),
                      reinterpret_cast<const __half*>(lb2), thr_seed, n_tiles, (float)meld_knn16_error_coef(nprod, d), norm2_max, scale_info,
-                     tile_origin, k16_two_sided(), list, (long long)list_stride, cnt);
+                     tile_origin, 1, list, (long long)list_stride, cnt);
   MELD_LAUNCH_CHECK("knn16_step_list_kernel");
   return MELD_OK;
 }
@@ -2815,7 +2738,7 @@ static int k16_step_lists_direct_impl(const double* X, int64_t N, int d, const d
   MELD_LAUNCH_CHECK("knn16_tile_bounds_kernel(bits)");
   const int64_t n_tiles64 = (int64_t)ceil_div(n_q, 64) * wpr;
   hipLaunchKernelGGL(knn16_bits_transpose_and_kernel, dim3((unsigned)ceil_div(n_tiles64, 4)), dim3(256), 0, st, bits_a, bits_b, n_q, wpr, live);
-  hipLaunchKernelGGL(knn16_step_list_bits_kernel, dim3((unsigned)ceil_div(N, K16_BQ)), dim3(256), 0, st, live, wpr, n_t, 0, k16_two_sided(), list,
+  hipLaunchKernelGGL(knn16_step_list_bits_kernel, dim3((unsigned)ceil_div(N, K16_BQ)), dim3(256), 0, st, live, wpr, n_t, 0, 1, list,
                      (long long)list_stride, cnt);
   MELD_LAUNCH_CHECK("knn16_step_list_bits_kernel");
   return MELD_OK;
@@ -2839,62 +2762,10 @@ extern "C" int meld_knn16_step_lists_direct_lead(const double* X, int64_t N, int
                                     lead_only, stream);
 }
 
-// Start values for the thresholds of meld_knn16_topk's first pass (thr_init, scaled units, roundup(q_count, BQ)
-// floats) from every query's own block of BQ cells; q_begin must be a multiple of BQ.  knn, radius_factor as for the
-// radius cut.  Rows whose block holds fewer than knn + 1 cells (or knn + 1 > 64) get +inf.
-extern "C" int meld_knn16_seed_thresholds(const double* X, int64_t N, int d, const double* mean, const float* scale_info,
-                                          const float* norm2_max, int64_t q_begin, int64_t q_count, int knn,
-                                          double radius_factor, int nprod, float* thr_init, meld_stream_t stream) {
-  MELD_CHECK_ARG(X && mean && scale_info && norm2_max && thr_init && N > 0 && q_count > 0 && q_begin >= 0 &&
-                     q_begin + q_count <= N,
-                 "meld_knn16_seed_thresholds: bad arguments");
-  MELD_CHECK_ARG(q_begin % K16_BQ == 0, "meld_knn16_seed_thresholds: q_begin must be a multiple of the query block (%d)", K16_BQ);
-  MELD_CHECK_ARG(knn >= 1 && radius_factor >= 1.0 && (nprod == 1 || nprod == 3), "meld_knn16_seed_thresholds: bad kernel parameters");
-  if (meld_knn16_kblocks(d) < 0) return MELD_ERR_UNSUPPORTED;
-  const int n_b = (int)ceil_div(q_count, K16_BQ);
-  hipStream_t st = S(stream);
-  if (knn + 1 > SEED_KMAX || d > 144) {  // no seed: the search starts at +inf as before
-    const size_t n = (size_t)n_b * K16_BQ;
-    MELD_HIP_CALL(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(thr_init), 0x7f800000, n, st));
-    return MELD_OK;
-  }
-  const float rf2 = (float)(radius_factor * radius_factor * (1.0 + 1e-6));
-#define K16_SEED_LAUNCH2(KV, DV)                                                                                          \
-  do {                                                                                                                    \
-    const size_t lds = sizeof(float) * (size_t)K16_BQ * DV;                                                               \
-    if (lds > 64 * 1024)                                                                                                  \
-      MELD_HIP_CALL(hipFuncSetAttribute(reinterpret_cast<const void*>(&knn16_seed_kernel<KV, DV>),                        \
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));                           \
-    hipLaunchKernelGGL((knn16_seed_kernel<KV, DV>), dim3(n_b), dim3(256), lds, st, X, N, d, mean, scale_info, norm2_max,   \
-                       q_begin, q_count, knn + 1, rf2, (float)meld_knn16_error_coef_const(nprod, d),                      \
-                       (float)meld_knn16_error_coef_lin(nprod), thr_init);                                                \
-  } while (0)
-#define K16_SEED_LAUNCH(KV)        \
-  do {                             \
-    if (d <= 60)                   \
-      K16_SEED_LAUNCH2(KV, 60);    \
-    else if (d <= 104)             \
-      K16_SEED_LAUNCH2(KV, 104);   \
-    else                           \
-      K16_SEED_LAUNCH2(KV, 144);   \
-  } while (0)
-  if (knn + 1 <= 8) {
-    K16_SEED_LAUNCH(8);
-  } else if (knn + 1 <= 16) {
-    K16_SEED_LAUNCH(16);
-  } else if (knn + 1 <= 32) {
-    K16_SEED_LAUNCH(32);
-  } else {
-    K16_SEED_LAUNCH(64);
-  }
-#undef K16_SEED_LAUNCH
-#undef K16_SEED_LAUNCH2
-  MELD_LAUNCH_CHECK("knn16_seed_kernel");
-  return MELD_OK;
-}
-
-// The same from the fp16 operands of meld_knn16_prepare, on the matrix pipe, over the query block's own tiles and four
-// on either side (see knn16_seed_mfma_kernel).  Q16 / Qn / Rt16 / scale_info / norm2_max as for meld_knn16_topk.
+// Start values for the thresholds of meld_knn16_topk's first pass (thr_init, scaled units, roundup(q_count, BQ) floats) from
+// the fp16 operands of meld_knn16_prepare, on the matrix pipe, over the query block's own tiles and `side_tiles` on either side
+// (see knn16_seed_mfma_kernel); q_begin must be a multiple of BQ.  knn, radius_factor as for the radius cut; knn + 1 > SEED_KMAX:
+// every row +inf.  Q16 / Qn / Rt16 / scale_info / norm2_max as for meld_knn16_topk.
 extern "C" int meld_knn16_seed_thresholds_mfma(const void* Q16, const float* Qn, const void* Rt16, const float* scale_info,
                                                const float* norm2_max, int64_t n_ref, int d, int64_t q_begin,
                                                int64_t q_count, int knn, double radius_factor, int nprod, int side_tiles,
@@ -3003,7 +2874,6 @@ static int k16_topk_impl(const void* Q16, const float* Qn, const void* Rt16, con
     MELD_CHECK_ARG(batch_every >= 0 && (batch_every & (batch_every - 1)) == 0, "MELD_KNN16_BATCH_EVERY must be a power of two");
   }
   if (const char* e = meld_dev_getenv("MELD_KNN16_BATCH_SLACK")) batch_slack = std::max(0, atoi(e));
-  const int two_sided = k16_two_sided();
   if (meld_dev_getenv("MELD_KNN16_STATS")) {  // profiling hook: selection counters, printed after the launch
     static unsigned long long* counters[64] = {nullptr};  // (a racing first call leaks 256 B at worst)
     int dev = 0;
@@ -3028,7 +2898,7 @@ static int k16_topk_impl(const void* Q16, const float* Qn, const void* Rt16, con
   ka.tile_origin = tile_origin;
   ka.batch_every = batch_every;
   ka.batch_slack = batch_slack;
-  ka.two_sided = two_sided;
+  ka.two_sided = 1;
   ka.stats = stats;
   ka.thr_init = thr_init;
   ka.knn1 = knn1;
@@ -3049,15 +2919,10 @@ static int k16_topk_impl(const void* Q16, const float* Qn, const void* Rt16, con
   // nothing and costs 15 %); MELD_KNN16_EE=0 / 1 overrides the caller, for A-B measurements
   const int dA = k16_dA(d, KB);
   const char* ee_env = meld_dev_getenv("MELD_KNN16_EE");
-  const char* ee_max = meld_dev_getenv("MELD_KNN16_EE_MAXKB");  // (development: the widest operand the partial-test kernel is taken for)
-  const bool ee = step_list != nullptr && dA > 0 && KB >= 2 && KB <= (ee_max ? atoi(ee_max) : 7) && (ee_env ? atoi(ee_env) != 0 : partial_test != 0);
+  const bool ee = step_list != nullptr && dA > 0 && KB >= 2 && KB <= 7 && (ee_env ? atoi(ee_env) != 0 : partial_test != 0);
   ka.ee_hi = 16 + d - dA;
   ka.count_go = two_counters;  // (a caller of meld_knn16_topk_listed passes ONE counter, whatever MELD_KNN16_EE forces)
-  {
-    const int slots_used = dA > 0 ? 16 + (d - dA) + 3 : d + 3;
-    const char* sk = meld_dev_getenv("MELD_KNN16_SKIP_PAD");  // (=0: copy the padding plane as before, for A-B measurements)
-    ka.planes_used = (sk && atoi(sk) == 0) ? 2 * KB : (slots_used + 7) / 8;
-  }
+  ka.planes_used = ((dA > 0 ? 16 + (d - dA) + 3 : d + 3) + 7) / 8;  // (the padding plane behind the used K slots is never copied)
 #ifndef K16_PROFILING
   MELD_CHECK_ARG(abl == 0, "MELD_KNN16_ABLATION needs a library built with -DK16_PROFILING");
 #endif

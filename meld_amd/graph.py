@@ -9,17 +9,18 @@ kernels of ``libmeld_hip.so``; torch only owns the device memory and the stream.
 """
 from __future__ import annotations
 
-from ._options import is_set, opt
+from ._options import opt
 
 import math
-import os
-import sys
 import time
+
+from types import SimpleNamespace
 
 import numpy as np
 import torch
 
 from ._lib import check, get_lib, ptr
+from .knn_plan import SearchOptions, plan_knn_search, search_nprod, sphere_layout
 
 __all__ = ["DeviceGraph", "build_knn_graph", "default_ksel", "EVENTS", "record_events"]
 
@@ -427,6 +428,11 @@ def _eigh_one_thread(a):
         return np.linalg.eigh(a, UPLO="U")
 
 
+def _radius_factor(decay, thresh):
+    """Kernel radius in bandwidths: the distance at which the alpha-decay kernel falls to ``thresh``."""
+    return 1.0 if math.isinf(decay) else float((-math.log(thresh)) ** (1.0 / decay))
+
+
 def _scan_i32(lib, x, st):
     n = x.shape[0]
     out = torch.empty(n + 1, dtype=torch.int64, device=x.device)
@@ -448,34 +454,10 @@ class HipOps:
         # recurrence kernel: "auto" (panel-tiled layout for graphs of at least PT_MIN_ROWS local rows),
         # "tiled" (always), "csr" (the CSR-stream kernel of spmm.hip)
         self.spmm = spmm
-        # precision of the f16x3 search on the coordinate K blocks: 1 = fp16 hi parts only (half the MFMAs,
-        # error bound 2^-9 max|x|^2), 3 = full hi/lo split (2^-16).  Either way the result is exact: rows
-        # the bound cannot certify go through the exact sweep.
-        self.nprod = int(opt("MELD_KNN_NPROD", "1")) if nprod is None else int(nprod)
-        # exact tile pruning in the f16x3 search: off by default -- on the 10-d-intrinsic benchmark mixture
-        # the bounding spheres of 64-cell tiles (radius 0.72) dwarf the neighbour radius (0.63), 98 % of
-        # the (workgroup, tile) pairs stay live and the table costs 3 ms; it pays on low-dimensional or
-        # well-separated data
-        self.prune = (opt("MELD_KNN_PRUNE", "1") != "0") if prune is None else bool(prune)
-        self.radius_cut = opt("MELD_KNN_RADIUS_CUT", "1") != "0"
-        # thresholds of the first pass seeded from every row's own block (meld_knn16_seed_thresholds)
-        self.seed = opt("MELD_KNN_SEED", "1") != "0"
-        # per-query test of the pruning table against those seeds (meld_knn16_bounds, thr_seed)
-        self.seeded_bounds = opt("MELD_KNN_SEEDED_BOUNDS", "1") != "0"
-        # pruned search: query blocks dispatched by decreasing work (meld_knn16_block_work)
-        self.block_order = opt("MELD_KNN_BLOCK_ORDER", "1") != "0"
-        # the first pass walks precomputed step lists (meld_knn16_step_lists) instead of testing the pruning table step by step
-        self.step_lists = opt("MELD_KNN_STEP_LISTS", "1") != "0"
-        # the search runs in the cells' principal frame where that concentrates the distances in the leading coordinates (the
-        # list-driven first pass tests a block behind its first K block: principal_frame)
-        self.rotate = opt("MELD_KNN_ROTATE", "1") != "0"
-        # ... from this many cells on: the frame costs ~0.9 ms whatever the size (a read-back and a 50 x 50 eigenproblem on the host
-        # among it) and pays from ~250k cells (200k: 10.0 vs 9.8 ms per step without it; 350k: 14.6 vs 15.4; 500k: 21.0 vs 22.5)
-        self.rotate_min_cells = int(opt("MELD_KNN_ROTATE_MIN", "262144"))
-        # candidate-search kernel: "f16x3" (split-fp16 MFMA) or "f32" (fp32 MFMA)
-        self.search = search or opt("MELD_KNN_SEARCH", "f16x3")
-        if self.search not in ("f16x3", "f32"):
-            raise ValueError("unknown search kernel {!r}".format(self.search))
+        # options of the kNN search (meld_amd.knn_plan.SearchOptions): attributes, so that a test can switch one off
+        o = SearchOptions.from_env(search=search, prune=prune, nprod=nprod)
+        self.search, self.nprod, self.prune, self.rotate, self.rotate_min_cells = o.search, o.nprod, o.prune, o.rotate, o.rotate_min_cells
+        self.radius_cut, self.seed, self.seeded_bounds, self.block_order = o.radius_cut, o.seed, o.seeded_bounds, o.block_order
         if not torch.cuda.is_available():
             raise RuntimeError("meld_amd needs a ROCm GPU (MI355X); there is no CPU fallback")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -498,8 +480,7 @@ class HipOps:
         None where the frame will not be asked for (options, size, width) or the column sums are not at hand."""
         lib = self.lib
         N, d = int(X.shape[0]), int(X.shape[1])
-        if (col_stats is None or opt("MELD_FRAME_ASYNC", "1") == "0" or not self.rotate or not self.prune or not self.step_lists or not self.seed or self.nprod != 1 or self.search != "f16x3"
-                or N < max(16384, self.rotate_min_cells) or d > int(lib.meld_frame_max_dims()) or int(lib.meld_knn16_split_dims(d)) <= 0):
+        if col_stats is None or d > int(lib.meld_frame_max_dims()) or not plan_knn_search(lib, N, d, 0, N, 1, 2, options=self).frame:
             return None
         st = _stream()
         mean = col_stats[0] / N
@@ -591,487 +572,447 @@ class HipOps:
         before the search, which starts its thresholds there and cuts nothing on its own.  ``knn_max`` ([UPSTREAM kNNGraph
         ``knn_max``]): a row keeps its knn_max nearest cells (besides itself) at most.  ``count_rows_ge``: report the number of rows
         whose kernel radius holds at least that many cells, self counted (``info["rows_with_at_least"]``: what graphtools'
-        re-search loop branches on, see ``build_knn_graph``)."""
-        lib, st, dev = self.lib, _stream(), X.device
-        tm = tm or _Timer(False)
-        N, d = int(X.shape[0]), int(X.shape[1])
-        cross = n_refs is not None
-        NR = int(n_refs) if cross else N  # references of the search
-        if cross and not (0 < NR <= q_begin and q_begin + q_count <= N):
+        re-search loop branches on, see ``build_knn_graph``).
+
+        The route (search back end, frame, seeds, pruning, lists, slices, filter pass) is ``meld_amd.knn_plan.plan_knn_search``'s;
+        the stages run in this order: search operands, start thresholds, step lists, candidate search, refinement (+ the
+        full-precision re-search), exact sweep, emit."""
+        N = int(X.shape[0])
+        NR = int(n_refs) if n_refs is not None else N  # references of the search
+        if n_refs is not None and not (0 < NR <= q_begin and q_begin + q_count <= N):
             raise ValueError("cross search: the queries must lie behind the n_refs references")
-        tm.start()
+        a = SimpleNamespace(X=X, N=N, d=int(X.shape[1]), NR=NR, cross=n_refs is not None, q_begin=q_begin, q_count=q_count, knn=knn, decay=decay,
+                            thresh=thresh, bw_scale=bw_scale, bw_fixed=bw_fixed, knn_max=knn_max, force_fallback=force_fallback,
+                            col_stats=col_stats, frame_axes=frame_axes, tm=tm or _Timer(False))
+        r = self._search_and_refine(a, ksel, comm)
+        retry_from = None
+        if r.n_flag > max(1024, q_count // 100) and ksel < 128 and r.plan.search == "f16x3" and not force_fallback:
+            # Many uncertified rows with a short candidate list (dense low-dimensional data: more than ksel cells inside the radius
+            # inflated by the search-error allowance): search once more with the longest list instead of sweeping them one by one
+            # (1M cells in the plane, knn = 15: 292k rows through the sweep at ksel = 64, 0.63 s; none at ksel = 128, 32 ms).  Same
+            # graph either way.  (comm is NOT forwarded on purpose: only the ranks that need the retry take it, so it must not issue
+            # collectives -- the shared-spheres all-gather of the first try is skipped, every rank computes all spheres itself.)
+            retry_from, ksel = (ksel, r.n_flag), 128
+            r = self._search_and_refine(a, ksel, None)
+        s = self._exact_sweep(a, r, count_rows_ge)
+        keys, vals, assembled = self._emit(a, r, s, ksel, assemble, symm)
+        p, c = r.plan, r.cands
+        info = dict(ksel=int(ksel), KP=int(c.KP), search=p.search, nprod=p.nprod, n_flagged_rows=r.n_flag,
+                    # the route the search took (meld_amd.knn_plan.KnnPlan)
+                    prune=p.prune, radius_cut=p.radius_cut, seed=p.seed != "none", seeded_bounds=p.seeded_bounds, block_order=p.block_order != "none",
+                    step_lists=p.lists != "none", principal_frame=p.frame, two_phase=p.two_pass, n_rows_bandwidth_recomputed=s.n_rebandwidth,
+                    n_researched_rows=r.n_flag_stage1 if p.stage2 else 0, nnz_directed=r.m_main + s.fb_total,
+                    # (wave, tile) pairs the first search pass computed (all of them without pruning)
+                    wave_tiles_done=r.tiles_done_h, blocks_past_partial_test=r.blocks_on_h, pairs_past_filter=r.pairs_kept_h)
+        if s.rows_at_least is not None:
+            info["rows_with_at_least"] = s.rows_at_least
+        if assembled is not None:
+            info["assembled"] = assembled  # (rowptr, col, val) of the symmetrised rows: the caller skips assemble_rows
+        if retry_from is not None:
+            info["ksel_retry_from"], info["n_flagged_rows_first_try"] = int(retry_from[0]), int(retry_from[1])
+        return keys, vals, r.bw, info
+
+    def _search_and_refine(self, a, ksel, comm):
+        """One pass of candidate search + exact refinement at candidate-list length ``ksel``: the plan, the candidates and the refined
+        rows, with the one read-back of the scalars the host needs next."""
+        lib, dev = self.lib, a.X.device
+        nprod = search_nprod(self.nprod, a.d)
+        resident = lib.meld_knn16_resident_blocks(a.d, nprod) if lib.meld_knn16_kblocks(a.d) > 0 and nprod in (1, 3) else 0
+        plan = plan_knn_search(lib, a.N, a.d, a.q_begin, a.q_count, a.knn, ksel, options=self, cross=a.cross, bandwidth=a.bw_fixed is not None,
+                               world=getattr(comm, "world", 1) if comm is not None else 1, resident=resident)
+        a.tm.start()
         col_min = col_max = None
-        if col_stats is not None:  # (the front end's pass over X -- its NaN / infinity check -- already has them)
-            sums, col_min, col_max = col_stats
-            mean = sums / N
-        elif d <= 256:
+        if a.col_stats is not None:  # (the front end's pass over X -- its NaN / infinity check -- already has them)
+            sums, col_min, col_max = a.col_stats
+            mean = sums / a.N
+        elif a.d <= 256:
             # one pass: the mean and the columns' extremes (from which the operand scale follows without another pass over X)
-            sums, col_min, col_max = self.col_stats(X)
-            mean = sums / N
+            sums, col_min, col_max = self.col_stats(a.X)
+            mean = sums / a.N
         else:  # beyond the column-sum kernel's width (only the library search path handles such data)
-            mean = X.mean(dim=0)
-        norm2 = torch.empty(N, dtype=torch.float32, device=dev)
+            mean = a.X.mean(dim=0)
+        norm2 = torch.empty(a.N, dtype=torch.float32, device=dev)
         nmax = torch.zeros(1, dtype=torch.float32, device=dev)
-        X_search, mean_search = X, mean  # (the f16x3 search may move to the cells' principal frame)
-        search = self.search
-        cand_thr, rfac, tiles_done = None, 1.0, None
-        used_prune = used_seed = used_seeded_bounds = used_block_order = used_step_lists = used_two_phase = False
-        partial_in_search = 0
-        if search == "f16x3" and lib.meld_knn16_kblocks(d) < 0:
-            search = "wide"  # d beyond the instantiated MFMA kernels (d > 141)
-        if cross and search != "f16x3":
-            raise NotImplementedError("the search between two point sets runs on the split-fp16 MFMA kernel only (d <= 141)")
-        if search == "wide":
-            # Library path for wide data that was not reduced by PCA: chunked fp64 GEMMs (rocBLAS) for
-            # |q|^2 + |r|^2 - 2 q.r and torch.topk merges, feeding the same exact refinement.  No hand-written
-            # kernel: the reference's default (n_pca = 100) never gets here, and the distance GEMM at d >> 100 is
-            # a plain library GEMM.
-            research = None
-            cap = int(ksel)
-            err_coef, err_lin = 1e-6, 0.0  # fp64 GEMM form + fp32 storage of d2: << 1e-6 max|x~|^2
-            Xc = X - mean
-            n2 = (Xc * Xc).sum(dim=1)
-            norm2.copy_(n2.to(torch.float32))
-            nmax.copy_(n2.max().to(torch.float32).reshape(1))
-            tm.stop("prepare")
-            kk = min(int(ksel), N)
-            cand_idx = torch.zeros(q_count * cap, dtype=torch.int32, device=dev)
-            cand_d2 = torch.full((q_count * cap,), float("inf"), dtype=torch.float32, device=dev)
-            cand_cnt = torch.full((q_count,), kk, dtype=torch.int32, device=dev)
-            QC, RC = 4096, 32768
-            with _EventSpan("knn_topk", N=N, d=d, q=q_count):
-                for q0 in range(0, q_count, QC):
-                    q1 = min(q_count, q0 + QC)
-                    Xq = Xc[q_begin + q0 : q_begin + q1]
-                    nq = n2[q_begin + q0 : q_begin + q1]
-                    best_d = torch.full((q1 - q0, 0), 0.0, dtype=torch.float64, device=dev)
-                    best_i = torch.zeros((q1 - q0, 0), dtype=torch.int64, device=dev)
-                    for r0 in range(0, N, RC):
-                        r1 = min(N, r0 + RC)
-                        D = nq[:, None] + n2[None, r0:r1] - 2.0 * (Xq @ Xc[r0:r1].T)
-                        ids = torch.arange(r0, r1, device=dev, dtype=torch.int64)[None, :].expand(q1 - q0, -1)
-                        D = torch.cat([best_d, D], dim=1)
-                        ids = torch.cat([best_i, ids], dim=1)
-                        best_d, sel = torch.topk(D, min(kk, D.shape[1]), dim=1, largest=False, sorted=True)
-                        best_i = torch.gather(ids, 1, sel)
-                    rows = torch.arange(q0, q1, device=dev, dtype=torch.int64)[:, None] * cap + torch.arange(kk, device=dev)[None, :]
-                    cand_d2[rows.reshape(-1)] = best_d.clamp_(min=0.0).to(torch.float32).reshape(-1)
-                    cand_idx[rows.reshape(-1)] = best_i.to(torch.int32).reshape(-1)
-            KP = d
-            Q = Rt = None
-            del Xc
-        elif search == "f16x3":
-            # split-fp16 operands on v_mfma_f32_32x32x16_f16 (knn16.hip)
-            # In very low dimension the neighbours are so close (relative to max|x|^2) that the fp16-hi first
-            # pass certifies almost nothing (1M x 3: 968k of 1M rows re-searched) and is wasted; there the full
-            # split costs next to nothing (one K block), so it is used from the start.  Same result either way.
-            nprod = 3 if (self.nprod == 1 and d <= 6) else self.nprod
-            KB = lib.meld_knn16_kblocks(d)
-            if KB < 0:
-                check(KB, "meld_knn16_kblocks")
-            TS, BQ = lib.meld_knn16_tile_refs(), lib.meld_knn16_block_queries()
-            cap = lib.meld_knn16_row_capacity(ksel)
-            if cap < 0:
-                check(cap, "meld_knn16_row_capacity")
-            err_coef = lib.meld_knn16_error_coef_const(nprod, d)
-            err_lin = lib.meld_knn16_error_coef_lin(nprod)
-            n_tiles = (NR + TS - 1) // TS
-            q_pad = ((q_count + BQ - 1) // BQ) * BQ
-            # The frame of the search (X_s, its mean and column extremes): the cells' principal frame where the first pass can
-            # use it -- operands in the split layout, seeds and step lists, the whole graph or a row shard of it -- else X itself.
-            # Everything up to the candidate lists works on X_s; refinement and the exact sweeps on X.
-            lead = int(lib.meld_knn16_split_dims(d))
-            if (self.rotate and lead > 0 and nprod == 1 and not cross and self.prune and self.step_lists and self.seed
-                    and N >= max(16384, self.rotate_min_cells) and q_begin % BQ == 0 and bw_fixed is None):
-                X_s = self.principal_frame(X, mean, lead, comm, axes=frame_axes)
-                if X_s is not None:
-                    sums_s, col_min, col_max = self.col_stats(X_s)
-                    X_search, mean_search = X_s, sums_s / N
-            Rt = torch.empty(n_tiles * lib.meld_knn16_tile_bytes(d), dtype=torch.uint8, device=dev)
-            Q = torch.empty(q_pad * lib.meld_knn16_query_bytes(d), dtype=torch.uint8, device=dev)
-            Qn = torch.empty(q_pad, dtype=torch.float32, device=dev)
-            scale_info = torch.empty(4, dtype=torch.float32, device=dev)
-            if cross:
-                check(lib.meld_knn16_prepare_cross(ptr(X), NR, N, d, ptr(mean), q_begin, q_count, ptr(Rt), ptr(Q), ptr(Qn), ptr(norm2), ptr(nmax), ptr(scale_info), st), "meld_knn16_prepare_cross")
-                # the error bounds speak of the largest norm among ALL points of the search, and refine reads the
-                # query's own norm at its row
-                norm2[q_begin : q_begin + q_count] = Qn[:q_count]
-                nmax = torch.maximum(nmax, Qn[:q_count].max().reshape(1))
-            else:
-                if col_min is not None:
-                    check(lib.meld_knn16_prepare_scaled(ptr(X_search), N, d, ptr(mean_search), ptr(col_min), ptr(col_max), q_begin, q_count, ptr(Rt), ptr(Q), ptr(Qn), ptr(norm2), ptr(nmax), ptr(scale_info), st), "meld_knn16_prepare_scaled")
-                else:
-                    check(lib.meld_knn16_prepare(ptr(X_search), N, d, ptr(mean_search), q_begin, q_count, ptr(Rt), ptr(Q), ptr(Qn), ptr(norm2), ptr(nmax), ptr(scale_info), st), "meld_knn16_prepare")
-            tm.stop("prepare")
-            cand_idx = torch.empty(q_pad * cap, dtype=torch.int32, device=dev)
-            cand_d2 = torch.empty(q_pad * cap, dtype=torch.float32, device=dev)
-            cand_cnt = torch.empty(q_pad, dtype=torch.int32, device=dev)
-            if self.radius_cut and knn < ksel:
-                # rows are cut at the kernel radius their (knn+1)-th neighbour so far implies; the search
-                # publishes each row's final threshold for refine's completeness test
-                cand_thr = torch.full((q_pad,), float("inf"), dtype=torch.float32, device=dev)
-                rfac = 1.0 if math.isinf(decay) else float((-math.log(thresh)) ** (1.0 / decay))
-                # (the cut keeps everything within max(rf * bandwidth_scale, 1) bandwidths: never less than the bandwidth entry)
-                rfac = max(rfac * float(bw_scale), 1.0)
-            lb2 = block_order = step_list = step_cnt = None
-            tiles_done = torch.zeros(4, dtype=torch.int64, device=dev)  # [(wave, tile) pairs looked at, blocks of 32 references past the partial test (two-pass route: pairs the search computed, then its blocks)]
-            will_prune = self.prune and q_begin % TS == 0 and N >= 16384 and not cross
-            n_blocks = q_pad // BQ
-            seeds = None
-            knn_cut = knn  # the radius cut of the search follows the knn-th neighbour ...
-            if bw_fixed is not None and cand_thr is not None:
-                # ... unless the bandwidth is given: every row's radius is known, the thresholds start there (scaled units, with
-                # the row's search-error allowance on top) and the search cuts nothing itself (knn_cut = 0)
-                knn_cut = 0
-                rf_real = 1.0 if math.isinf(decay) else float((-math.log(thresh)) ** (1.0 / decay))
-                rad = (bw_fixed[q_begin : q_begin + q_count] * float(bw_scale)).clamp_(min=float(np.finfo(float).eps)) * rf_real
-                nmx = nmax.to(torch.float64)
-                e_row = float(err_coef) * nmx + float(err_lin) * torch.sqrt(norm2[q_begin : q_begin + q_count].to(torch.float64) * nmx)
-                seeds = torch.full((q_pad,), float("inf"), dtype=torch.float32, device=dev)
-                seeds[:q_count] = ((rad * rad + 1.01 * e_row) * scale_info[0].to(torch.float64) ** 2 * (1.0 + 1e-5)).to(torch.float32)
-                if q_pad > q_count:
-                    seeds[q_count:] = seeds[q_count - 1]
-            elif self.seed and cand_thr is not None and q_begin % BQ == 0 and not cross:
-                # every row starts at the kernel radius its own block of BQ cells implies instead of at +inf
-                seeds = torch.empty(q_pad, dtype=torch.float32, device=dev)
-                if opt("MELD_KNN_SEED", "1") == "2":  # the fp32 kernel over the own block only
-                    check(lib.meld_knn16_seed_thresholds(ptr(X_search), N, d, ptr(mean_search), ptr(scale_info), ptr(nmax), q_begin, q_count, knn, rfac, nprod, ptr(seeds), st), "meld_knn16_seed_thresholds")
-                else:
-                    check(lib.meld_knn16_seed_thresholds_mfma(ptr(Q), ptr(Qn), ptr(Rt), ptr(scale_info), ptr(nmax), N, d, q_begin, q_count, knn, rfac, nprod, int(opt("MELD_KNN_SEED_SIDE", "0")), ptr(seeds), st), "meld_knn16_seed_thresholds_mfma")
-                tm.stop("seed")
-                if opt("MELD_KNN_SEEDS_FROM"):  # (development: what perfect start thresholds would be worth -- the final thresholds of an earlier run)
-                    seeds = torch.minimum(seeds, torch.load(opt("MELD_KNN_SEEDS_FROM")).to(dev))
-            if will_prune:
-                # (after the seeds: with them the table also drops the tiles no query of a wave can reach from
-                # its own start threshold, see meld_knn16_bounds)
-                tb = lib.meld_knn16_bounds_temp_bytes(N, d, q_count)
-                tmpb = torch.empty(tb, dtype=torch.uint8, device=dev)
-                spheres_shared = False
-                if comm is not None and getattr(comm, "world", 1) > 1:
-                    # row-sharded build: the spheres of the reference tiles are the same on every rank (0.7 ms at 1M cells):
-                    # every rank computes 1 / world of them and the three arrays are all-gathered (4 MB in all)
-                    import ctypes as C
-
-                    rows_c, row_b = C.c_int64(0), C.c_int64(0)
-                    check(lib.meld_knn16_sphere_layout(N, d, C.byref(rows_c), C.byref(row_b)), "meld_knn16_sphere_layout")
-                    rows_c, row_b = int(rows_c.value), int(row_b.value)
-                    if rows_c % comm.world == 0:
-                        per = rows_c // comm.world
-                        t0s = min(comm.rank * per, n_tiles)
-                        t1s = min(t0s + per, n_tiles)
-                        tmpb.zero_()
-                        check(lib.meld_knn16_tile_spheres(ptr(X_search), N, d, ptr(mean_search), ptr(scale_info), ptr(tmpb), t0s, max(t1s - t0s, 0), st), "meld_knn16_tile_spheres")
-                        parts = (tmpb[: rows_c * row_b], tmpb[rows_c * row_b : rows_c * (row_b + 4)], tmpb[rows_c * (row_b + 4) : rows_c * (row_b + 8)])
-                        for arr, width in zip(parts, (row_b, 4, 4)):
-                            mine = arr[comm.rank * per * width : (comm.rank + 1) * per * width].clone()
-                            comm.all_gather_rows(arr, mine)
-                        spheres_shared = True
-                seeded_bounds = seeds is not None and self.seeded_bounds
-                # (few query blocks -- a row shard, a mid-sized data set -- are searched in reference slices: a slice of a list-driven
-                # launch walks every S-th entry of the block's list, MELD_KNN_LIST_SLICES=0 sends them to the table-driven kernel)
-                resident_all = lib.meld_knn16_resident_blocks(d, nprod)
-                few_blocks = resident_all > 0 and n_blocks < 2 * resident_all
-                want_lists = self.step_lists and seeds is not None and cand_thr is not None and nprod == 1 \
-                    and not (few_blocks and opt("MELD_KNN_LIST_SLICES", "1") == "0")
-                direct = want_lists and seeded_bounds and not spheres_shared and q_begin == 0 and q_count == N and not cross \
-                    and opt("MELD_KNN_LIST_DIRECT", "1") != "0" and not opt("MELD_KNN_SYMMETRIC_BOUNDS_OFF")
-                if direct:
-                    # queries = all the cells: the lists come straight from the cells (bounds as two bits per (wave, tile); the fp16
-                    # table, its symmetrisation pass and the list builder's pass over it never exist)
-                    step_list = torch.empty(n_blocks * n_tiles, dtype=torch.int32, device=dev)
-                    step_cnt = torch.empty(n_blocks, dtype=torch.int32, device=dev)
-                    scratch = torch.empty(lib.meld_knn16_list_scratch_bytes(N), dtype=torch.uint8, device=dev)
-                    check(lib.meld_knn16_step_lists_direct_lead(ptr(X_search), N, d, ptr(mean_search), ptr(scale_info), ptr(nmax), ptr(Rt), ptr(seeds), ptr(Qn), nprod,
-                                                                ptr(tmpb), ptr(scratch), ptr(step_list), n_tiles, ptr(step_cnt), int(X_search is not X), st), "meld_knn16_step_lists_direct")
-                    del scratch
-                    work = step_cnt
-                else:
-                    lb2 = torch.empty(lib.meld_knn16_bounds_bytes(N, q_count), dtype=torch.uint8, device=dev)
-                    check((lib.meld_knn16_bounds_from_spheres if spheres_shared else lib.meld_knn16_bounds)(ptr(X_search), N, d, ptr(mean_search), ptr(scale_info), ptr(nmax), ptr(Rt), q_begin, q_count, ptr(seeds) if seeded_bounds else None, ptr(Qn) if seeded_bounds else None, nprod, ptr(tmpb), ptr(lb2), st), "meld_knn16_bounds")
-                if direct:
-                    pass
-                elif want_lists:
-                    # the tiles a block can rule out at its start thresholds, written down once (the count is the block's work)
-                    step_list = torch.empty(n_blocks * n_tiles, dtype=torch.int32, device=dev)
-                    step_cnt = torch.empty(n_blocks, dtype=torch.int32, device=dev)
-                    check(lib.meld_knn16_step_lists(ptr(lb2), ptr(seeds), N, d, q_count, nprod, ptr(nmax), ptr(scale_info), 0 if cross else q_begin,
-                                                    ptr(step_list), n_tiles, ptr(step_cnt), st), "meld_knn16_step_lists")
-                    work = step_cnt
-                elif self.block_order and n_blocks > 1:
-                    # longest query blocks first (the dispatch follows the block index): see meld_knn16_block_work
-                    work = torch.empty(n_blocks, dtype=torch.int32, device=dev)
-                    check(lib.meld_knn16_block_work(ptr(lb2), ptr(seeds), N, d, q_count, nprod, ptr(nmax), ptr(scale_info), ptr(work), st), "meld_knn16_block_work")
-                else:
-                    work = None
-                if self.block_order and work is not None and n_blocks > 1:
-                    block_order = torch.argsort(work, descending=True, stable=True).to(torch.int32)
-                tm.stop("bounds")
-            # Few query blocks (a row shard, a mid-sized data set): with pruning the work of a block varies 12-fold and a
-            # launch that fills the chip less than twice over ends when its heaviest block does (a 1/8 shard of 1M cells:
-            # 7-10 ms instead of 26 / 8).  The references are then cut into slices -- blocks x slices workgroups, each
-            # with its own candidate rows, merged afterwards -- so that the heavy blocks are shared out.
-            main_slices = 1
-            if will_prune and cand_thr is not None:
-                resident = lib.meld_knn16_resident_blocks(d, nprod)
-                if opt("MELD_KNN_MAIN_SLICES"):
-                    main_slices = int(opt("MELD_KNN_MAIN_SLICES"))
-                elif resident > 0 and n_blocks < 2 * resident:
-                    main_slices = int(max(1, min(4, lib.meld_knn16_max_slices(ksel), -(-2 * resident // n_blocks), n_tiles // 64)))  # (more slices cost more in merging than they balance)
-            # The partial-distance test of the principal frame as a pass of its own (meld_knn16_partial_filter): every listed (wave,
-            # tile) pair is tested on K block 0 against the row's start threshold and the lists are thinned in place; the search
-            # then stages whole tiles for the quarter of the pairs that survive (it keeps its own test per block of 32 references:
-            # 30 % of the blocks of a surviving pair still stop behind K block 0).  MELD_KNN_TWO_PHASE=0: the round-5 form, every
-            # listed tile staged in full by the one kernel that tests and searches.
-            # (few query blocks -- a row shard, a mid-sized data set: main_slices > 1 -- keep the one-kernel form: a workgroup of the
-            # filter pass walks its block's whole list, and a launch that fills the chip less than twice over ends when its longest
-            # list does -- a 1/8 shard of 1M cells: 2.4-3.0 ms for the filter alone against 3.0 ms for the sliced search)
-            two_phase = (step_list is not None and X_search is not X and seeds is not None
-                         and (main_slices == 1 or opt("MELD_KNN_TWO_PHASE") == "2")
-                         and opt("MELD_KNN_TWO_PHASE", "1") != "0" and opt("MELD_KNN16_EE") is None)
-            partial_in_search = int(X_search is not X)
-            tiles_b = tiles_done
-            if two_phase:
-                with _EventSpan("knn_filter", N=N, d=d, q=q_count):
-                    check(lib.meld_knn16_partial_filter(ptr(Q), ptr(Qn), ptr(Rt), ptr(scale_info), ptr(nmax), d, q_count, ptr(seeds), ptr(step_list),
-                                                        ptr(step_cnt), n_tiles, ptr(step_cnt), ptr(tiles_done), ptr(block_order), st), "meld_knn16_partial_filter")
-                    if block_order is not None:  # (longest blocks first, by what is left of them)
-                        block_order = torch.argsort(step_cnt, descending=True, stable=True).to(torch.int32)
-                tiles_b = tiles_done[1:]  # (the search counts the pairs it computes, and its blocks, behind the filter's)
-                if opt("MELD_KNN_LIST_STATS"):  # (development: how long the thinned lists are -- the longest one bounds the search from below)
-                    sc = step_cnt.to(torch.float64)
-                    print("[lists behind the filter] blocks %d  entries: mean %.0f  median %.0f  p90 %.0f  p99 %.0f  max %.0f" % (
-                        sc.numel(), sc.mean(), sc.median(), torch.quantile(sc, 0.9), torch.quantile(sc, 0.99), sc.max()), file=sys.stderr)
-                tm.stop("knn_filter")
-            with _EventSpan("knn_topk", N=N, d=d, q=q_count):
-                if main_slices > 1:
-                    s_idx = torch.empty(main_slices * q_pad * cap, dtype=torch.int32, device=dev)
-                    s_d2 = torch.empty(main_slices * q_pad * cap, dtype=torch.float32, device=dev)
-                    s_cnt = torch.empty(main_slices * q_pad, dtype=torch.int32, device=dev)
-                    s_thr = torch.full((main_slices, q_pad), float("inf"), dtype=torch.float32, device=dev)
-                    if step_list is not None:
-                        check(lib.meld_knn16_topk_listed_partial(ptr(Q), ptr(Qn), ptr(Rt), ptr(scale_info), NR, d, q_count, ksel, ptr(step_list), ptr(step_cnt), n_tiles, ptr(nmax), 0 if cross else q_begin, ptr(seeds), knn_cut, rfac, ptr(s_idx), ptr(s_d2), ptr(s_cnt), ptr(s_thr), ptr(tiles_b), ptr(block_order), main_slices, partial_in_search, st), "meld_knn16_topk_listed(sliced)")
-                    else:
-                        check(lib.meld_knn16_topk(ptr(Q), ptr(Qn), ptr(Rt), ptr(scale_info), NR, d, q_count, ksel, nprod, main_slices, ptr(lb2), ptr(nmax), 0 if cross else q_begin, ptr(seeds), knn_cut, rfac, ptr(s_idx), ptr(s_d2), ptr(s_cnt), ptr(s_thr), ptr(tiles_done), ptr(block_order), st), "meld_knn16_topk(sliced)")
-                    check(lib.meld_knn16_merge_slices(ptr(s_idx), ptr(s_d2), ptr(s_cnt), q_count, ksel, main_slices, ptr(cand_idx), ptr(cand_d2), ptr(cand_cnt), st), "meld_knn16_merge_slices")
-                    cand_thr.copy_(s_thr.amin(0))  # the merged row holds every reference below the smallest slice threshold
-                    del s_idx, s_d2, s_cnt, s_thr
-                elif step_list is not None:
-                    check(lib.meld_knn16_topk_listed_partial(ptr(Q), ptr(Qn), ptr(Rt), ptr(scale_info), NR, d, q_count, ksel, ptr(step_list), ptr(step_cnt), n_tiles, ptr(nmax), 0 if cross else q_begin, ptr(seeds), knn_cut, rfac, ptr(cand_idx), ptr(cand_d2), ptr(cand_cnt), ptr(cand_thr), ptr(tiles_b), ptr(block_order), 1, partial_in_search, st), "meld_knn16_topk_listed")
-                else:
-                    check(lib.meld_knn16_topk(ptr(Q), ptr(Qn), ptr(Rt), ptr(scale_info), NR, d, q_count, ksel, nprod, 1, ptr(lb2), ptr(nmax), 0 if cross else q_begin, ptr(seeds), knn_cut, rfac, ptr(cand_idx), ptr(cand_d2), ptr(cand_cnt), ptr(cand_thr), ptr(tiles_done), ptr(block_order), st), "meld_knn16_topk")
-                # the search is the one long launch of the build (26 of 45 ms at 1M cells) and the host has nothing to do
-                # until its results are refined: work that does not depend on the graph (fit_transform's label
-                # factorisation: a host-blocking copy + a few small launches on a side stream) is started here
-                while _WHILE_SEARCHING:
-                    _WHILE_SEARCHING.pop()()
-            if opt("MELD_KNN_SAVE_THR") and cand_thr is not None:
-                torch.save((cand_thr * scale_info[0] ** 2 * 1.0001).cpu(), opt("MELD_KNN_SAVE_THR"))
-            used_prune, used_seed = lb2 is not None or step_list is not None, seeds is not None
-            used_seeded_bounds = bool(will_prune and seeds is not None and self.seeded_bounds)
-            used_block_order = block_order is not None
-            used_step_lists = step_list is not None
-            used_two_phase = bool(two_phase)
-            del lb2, step_list, step_cnt
-            KP = 16 * KB
-            research = dict(Rt=Rt, scale_info=scale_info, KB=KB, BQ=BQ) if nprod == 1 else None
+        if plan.search == "wide":
+            c = self._candidates_wide(a, plan, ksel, mean, norm2, nmax)
+        elif plan.search == "f32":
+            c = self._candidates_f32(a, plan, ksel, mean, norm2, nmax)
         else:
-            research = None
-            # fp32 operands on v_mfma_f32_32x32x2_f32 (knn.hip)
-            KP = lib.meld_knn_padded_dim(d)
-            if KP < 0:
-                check(KP, "meld_knn_padded_dim")
-            TS, BQ = lib.meld_knn_tile_refs(), lib.meld_knn_block_queries()
-            cap = lib.meld_knn_row_capacity(ksel)
-            if cap < 0:
-                check(cap, "meld_knn_row_capacity")
-            err_coef = lib.meld_knn_error_coef(d)
-            err_lin = 0.0
-            n_tiles = (N + TS - 1) // TS
-            Rt = torch.empty(n_tiles * KP * TS, dtype=torch.float32, device=dev)
-            check(lib.meld_knn_prepare_refs(ptr(X), N, d, ptr(mean), KP, ptr(Rt), ptr(norm2), ptr(nmax), st), "meld_knn_prepare_refs")
-            q_pad = ((q_count + BQ - 1) // BQ) * BQ
-            Q = torch.empty(q_pad * KP, dtype=torch.float32, device=dev)
-            check(lib.meld_knn_prepare_queries(ptr(X), N, d, ptr(mean), KP, q_begin, q_count, ptr(Q), st), "meld_knn_prepare_queries")
-            tm.stop("prepare")
-            cand_idx = torch.empty(q_pad * cap, dtype=torch.int32, device=dev)
-            cand_d2 = torch.empty(q_pad * cap, dtype=torch.float32, device=dev)
-            cand_cnt = torch.empty(q_pad, dtype=torch.int32, device=dev)
-            with _EventSpan("knn_topk", N=N, d=d, q=q_count):
-                check(lib.meld_knn_topk(ptr(Q), ptr(Rt), N, KP, q_count, ksel, ptr(cand_idx), ptr(cand_d2), ptr(cand_cnt), st), "meld_knn_topk")
-        tm.stop("knn_topk")
-        del Q
-        if research is None:
-            del Rt
+            c = self._candidates_f16x3(a, plan, ksel, comm, mean, col_min, col_max, norm2, nmax)
+        a.tm.stop("knn_topk")
+        return self._refine(a, c, ksel)
 
-        # exact refinement + alpha-decay kernel
-        max_rank = 0 if knn_max is None else int(knn_max) + 1  # (self counted, as graphtools counts it)
-        bw = torch.empty(q_count, dtype=torch.float64, device=dev)
-        cand_val = torch.empty(q_count * ksel, dtype=torch.float64, device=dev)
-        keep_cnt = torch.empty(q_count, dtype=torch.int32, device=dev)
-        flag_rows = torch.empty(q_count, dtype=torch.int32, device=dev)
+    def _candidates_wide(self, a, plan, ksel, mean, norm2, nmax):
+        """Library path for wide data that was not reduced by PCA: chunked fp64 GEMMs (rocBLAS) for |q|^2 + |r|^2 - 2 q.r and
+        torch.topk merges, feeding the same exact refinement.  No hand-written kernel: the reference's default (n_pca = 100) never
+        gets here, and the distance GEMM at d >> 100 is a plain library GEMM."""
+        dev, N, q_begin, q_count = a.X.device, a.N, a.q_begin, a.q_count
+        cap = int(ksel)
+        Xc = a.X - mean
+        n2 = (Xc * Xc).sum(dim=1)
+        norm2.copy_(n2.to(torch.float32))
+        nmax.copy_(n2.max().to(torch.float32).reshape(1))
+        a.tm.stop("prepare")
+        kk = min(int(ksel), N)
+        cand_idx = torch.zeros(q_count * cap, dtype=torch.int32, device=dev)
+        cand_d2 = torch.full((q_count * cap,), float("inf"), dtype=torch.float32, device=dev)
+        cand_cnt = torch.full((q_count,), kk, dtype=torch.int32, device=dev)
+        QC, RC = 4096, 32768
+        with _EventSpan("knn_topk", N=N, d=a.d, q=q_count):
+            for q0 in range(0, q_count, QC):
+                q1 = min(q_count, q0 + QC)
+                Xq = Xc[q_begin + q0 : q_begin + q1]
+                nq = n2[q_begin + q0 : q_begin + q1]
+                best_d = torch.full((q1 - q0, 0), 0.0, dtype=torch.float64, device=dev)
+                best_i = torch.zeros((q1 - q0, 0), dtype=torch.int64, device=dev)
+                for r0 in range(0, N, RC):
+                    r1 = min(N, r0 + RC)
+                    D = nq[:, None] + n2[None, r0:r1] - 2.0 * (Xq @ Xc[r0:r1].T)
+                    ids = torch.arange(r0, r1, device=dev, dtype=torch.int64)[None, :].expand(q1 - q0, -1)
+                    D = torch.cat([best_d, D], dim=1)
+                    ids = torch.cat([best_i, ids], dim=1)
+                    best_d, sel = torch.topk(D, min(kk, D.shape[1]), dim=1, largest=False, sorted=True)
+                    best_i = torch.gather(ids, 1, sel)
+                rows = torch.arange(q0, q1, device=dev, dtype=torch.int64)[:, None] * cap + torch.arange(kk, device=dev)[None, :]
+                cand_d2[rows.reshape(-1)] = best_d.clamp_(min=0.0).to(torch.float32).reshape(-1)
+                cand_idx[rows.reshape(-1)] = best_i.to(torch.int32).reshape(-1)
+        # (fp64 GEMM form + fp32 storage of d2: << 1e-6 max|x~|^2)
+        return SimpleNamespace(plan=plan, idx=cand_idx, d2=cand_d2, cnt=cand_cnt, thr=None, cap=cap, err_coef=1e-6, err_lin=0.0, KP=a.d,
+                               norm2=norm2, nmax=nmax, tiles_done=None, research=None)
+
+    def _candidates_f32(self, a, plan, ksel, mean, norm2, nmax):
+        """fp32 operands on v_mfma_f32_32x32x2_f32 (knn.hip)."""
+        lib, st, dev, X, N, d = self.lib, _stream(), a.X.device, a.X, a.N, a.d
+        KP = lib.meld_knn_padded_dim(d)
+        if KP < 0:
+            check(KP, "meld_knn_padded_dim")
+        TS, BQ = lib.meld_knn_tile_refs(), lib.meld_knn_block_queries()
+        cap = lib.meld_knn_row_capacity(ksel)
+        if cap < 0:
+            check(cap, "meld_knn_row_capacity")
+        n_tiles = (N + TS - 1) // TS
+        Rt = torch.empty(n_tiles * KP * TS, dtype=torch.float32, device=dev)
+        check(lib.meld_knn_prepare_refs(ptr(X), N, d, ptr(mean), KP, ptr(Rt), ptr(norm2), ptr(nmax), st), "meld_knn_prepare_refs")
+        q_pad = ((a.q_count + BQ - 1) // BQ) * BQ
+        Q = torch.empty(q_pad * KP, dtype=torch.float32, device=dev)
+        check(lib.meld_knn_prepare_queries(ptr(X), N, d, ptr(mean), KP, a.q_begin, a.q_count, ptr(Q), st), "meld_knn_prepare_queries")
+        a.tm.stop("prepare")
+        cand_idx = torch.empty(q_pad * cap, dtype=torch.int32, device=dev)
+        cand_d2 = torch.empty(q_pad * cap, dtype=torch.float32, device=dev)
+        cand_cnt = torch.empty(q_pad, dtype=torch.int32, device=dev)
+        with _EventSpan("knn_topk", N=N, d=d, q=a.q_count):
+            check(lib.meld_knn_topk(ptr(Q), ptr(Rt), N, KP, a.q_count, ksel, ptr(cand_idx), ptr(cand_d2), ptr(cand_cnt), st), "meld_knn_topk")
+        return SimpleNamespace(plan=plan, idx=cand_idx, d2=cand_d2, cnt=cand_cnt, thr=None, cap=cap, err_coef=lib.meld_knn_error_coef(d), err_lin=0.0,
+                               KP=KP, norm2=norm2, nmax=nmax, tiles_done=None, research=None)
+
+    def _candidates_f16x3(self, a, plan, ksel, comm, mean, col_min, col_max, norm2, nmax):
+        """Split-fp16 operands on v_mfma_f32_32x32x16_f16 (knn16.hip): operands, start thresholds, step lists, the search."""
+        lib, dev = self.lib, a.X.device
+        cap = lib.meld_knn16_row_capacity(ksel)
+        if cap < 0:
+            check(cap, "meld_knn16_row_capacity")
+        plan, o, nmax = self._operands16(a, plan, comm, mean, col_min, col_max, norm2, nmax)
+        c = SimpleNamespace(plan=plan, cap=cap, err_coef=lib.meld_knn16_error_coef_const(plan.nprod, a.d), err_lin=lib.meld_knn16_error_coef_lin(plan.nprod),
+                            KP=16 * o.KB, norm2=norm2, nmax=nmax, research=o if plan.stage2 else None)
+        c.idx = torch.empty(o.q_pad * cap, dtype=torch.int32, device=dev)
+        c.d2 = torch.empty(o.q_pad * cap, dtype=torch.float32, device=dev)
+        c.cnt = torch.empty(o.q_pad, dtype=torch.int32, device=dev)
+        c.thr, rfac = None, 1.0
+        if plan.radius_cut:
+            # rows are cut at the kernel radius their (knn+1)-th neighbour so far implies; the search publishes each row's final
+            # threshold for refine's completeness test (the cut keeps everything within max(rf * bandwidth_scale, 1) bandwidths)
+            c.thr = torch.full((o.q_pad,), float("inf"), dtype=torch.float32, device=dev)
+            rfac = max(_radius_factor(a.decay, a.thresh) * float(a.bw_scale), 1.0)
+        # [(wave, tile) pairs looked at, blocks of 32 references past the partial test (two-pass route: pairs the search computed,
+        # then its blocks)]
+        c.tiles_done = torch.zeros(4, dtype=torch.int64, device=dev)
+        seeds = self._start_thresholds(a, plan, o, c, rfac)
+        lists = self._step_lists(a, plan, o, seeds, nmax, comm)
+        self._search16(a, plan, o, c, ksel, seeds, rfac, lists)
+        return c
+
+    def _operands16(self, a, plan, comm, mean, col_min, col_max, norm2, nmax):
+        """The split-fp16 operands, in the cells' principal frame where the plan asks for it and the data carry one: everything up
+        to the candidate lists works on X_s, refinement and the exact sweeps on X.  Returns the plan as it stands after the frame's
+        test, the operands and the largest norm the error bounds speak of."""
+        lib, st, dev, X, N, d = self.lib, _stream(), a.X.device, a.X, a.N, a.d
+        KB, TS, BQ = lib.meld_knn16_kblocks(d), lib.meld_knn16_tile_refs(), lib.meld_knn16_block_queries()
+        o = SimpleNamespace(X_s=X, mean_s=mean, KB=KB, BQ=BQ, n_tiles=(a.NR + TS - 1) // TS, q_pad=((a.q_count + BQ - 1) // BQ) * BQ)
+        if plan.frame:
+            X_s = self.principal_frame(X, mean, int(lib.meld_knn16_split_dims(d)), comm, axes=a.frame_axes)
+            if X_s is None:
+                plan = plan.without_frame()
+            else:
+                sums_s, col_min, col_max = self.col_stats(X_s)
+                o.X_s, o.mean_s = X_s, sums_s / N
+        o.Rt = torch.empty(o.n_tiles * lib.meld_knn16_tile_bytes(d), dtype=torch.uint8, device=dev)
+        o.Q = torch.empty(o.q_pad * lib.meld_knn16_query_bytes(d), dtype=torch.uint8, device=dev)
+        o.Qn = torch.empty(o.q_pad, dtype=torch.float32, device=dev)
+        o.scale_info = torch.empty(4, dtype=torch.float32, device=dev)
+        tail = (a.q_begin, a.q_count, ptr(o.Rt), ptr(o.Q), ptr(o.Qn), ptr(norm2), ptr(nmax), ptr(o.scale_info), st)
+        if a.cross:
+            check(lib.meld_knn16_prepare_cross(ptr(X), a.NR, N, d, ptr(mean), *tail), "meld_knn16_prepare_cross")
+            # the error bounds speak of the largest norm among ALL points of the search, and refine reads the query's own norm at its row
+            norm2[a.q_begin : a.q_begin + a.q_count] = o.Qn[: a.q_count]
+            nmax = torch.maximum(nmax, o.Qn[: a.q_count].max().reshape(1))
+        elif col_min is not None:
+            check(lib.meld_knn16_prepare_scaled(ptr(o.X_s), N, d, ptr(o.mean_s), ptr(col_min), ptr(col_max), *tail), "meld_knn16_prepare_scaled")
+        else:
+            check(lib.meld_knn16_prepare(ptr(o.X_s), N, d, ptr(o.mean_s), *tail), "meld_knn16_prepare")
+        a.tm.stop("prepare")
+        return plan, o, nmax
+
+    def _start_thresholds(self, a, plan, o, c, rfac):
+        """Start thresholds of the first pass (scaled units) instead of +inf, or None."""
+        lib, st, dev = self.lib, _stream(), a.X.device
+        if plan.seed == "bandwidth":
+            # every row's radius is known: the thresholds start there, with the row's search-error allowance on top
+            rad = (a.bw_fixed[a.q_begin : a.q_begin + a.q_count] * float(a.bw_scale)).clamp_(min=float(np.finfo(float).eps)) * _radius_factor(a.decay, a.thresh)
+            nmx = c.nmax.to(torch.float64)
+            e_row = float(c.err_coef) * nmx + float(c.err_lin) * torch.sqrt(c.norm2[a.q_begin : a.q_begin + a.q_count].to(torch.float64) * nmx)
+            seeds = torch.full((o.q_pad,), float("inf"), dtype=torch.float32, device=dev)
+            seeds[: a.q_count] = ((rad * rad + 1.01 * e_row) * o.scale_info[0].to(torch.float64) ** 2 * (1.0 + 1e-5)).to(torch.float32)
+            if o.q_pad > a.q_count:
+                seeds[a.q_count :] = seeds[a.q_count - 1]
+            return seeds
+        if plan.seed == "mfma":
+            # every row starts at the kernel radius its own block of BQ cells (and its neighbour tiles) implies
+            seeds = torch.empty(o.q_pad, dtype=torch.float32, device=dev)
+            check(lib.meld_knn16_seed_thresholds_mfma(ptr(o.Q), ptr(o.Qn), ptr(o.Rt), ptr(o.scale_info), ptr(c.nmax), a.N, a.d, a.q_begin, a.q_count, a.knn,
+                                                      rfac, plan.nprod, 0, ptr(seeds), st), "meld_knn16_seed_thresholds_mfma")
+            a.tm.stop("seed")
+            return seeds
+        return None
+
+    def _step_lists(self, a, plan, o, seeds, nmax, comm):
+        """Exact tile pruning (after the seeds: with them the table also drops the tiles no query of a wave can reach from its own
+        start threshold, see meld_knn16_bounds).  Returns (bounds table, step lists, their lengths, dispatch order); all None
+        without pruning."""
+        if not plan.prune:
+            return None, None, None, None
+        lib, st, dev, N, d = self.lib, _stream(), a.X.device, a.N, a.d
+        X_s, mean_s, n_tiles, n_blocks = o.X_s, o.mean_s, o.n_tiles, o.q_pad // o.BQ
+        tmpb = torch.empty(lib.meld_knn16_bounds_temp_bytes(N, d, a.q_count), dtype=torch.uint8, device=dev)
+        if plan.bounds == "bounds_from_spheres":
+            # row-sharded build: the spheres of the reference tiles are the same on every rank (0.7 ms at 1M cells): every rank
+            # computes 1 / world of them and the three arrays are all-gathered (4 MB in all)
+            rows_c, row_b = sphere_layout(lib, N, d)
+            per = rows_c // comm.world
+            t0s = min(comm.rank * per, n_tiles)
+            t1s = min(t0s + per, n_tiles)
+            tmpb.zero_()
+            check(lib.meld_knn16_tile_spheres(ptr(X_s), N, d, ptr(mean_s), ptr(o.scale_info), ptr(tmpb), t0s, max(t1s - t0s, 0), st), "meld_knn16_tile_spheres")
+            parts = (tmpb[: rows_c * row_b], tmpb[rows_c * row_b : rows_c * (row_b + 4)], tmpb[rows_c * (row_b + 4) : rows_c * (row_b + 8)])
+            for arr, width in zip(parts, (row_b, 4, 4)):
+                mine = arr[comm.rank * per * width : (comm.rank + 1) * per * width].clone()
+                comm.all_gather_rows(arr, mine)
+        lb2 = step_list = step_cnt = None
+        if plan.lists == "direct":
+            # queries = all the cells: the lists come straight from the cells (bounds as two bits per (wave, tile); the fp16 table,
+            # its symmetrisation pass and the list builder's pass over it never exist)
+            step_list = torch.empty(n_blocks * n_tiles, dtype=torch.int32, device=dev)
+            step_cnt = torch.empty(n_blocks, dtype=torch.int32, device=dev)
+            scratch = torch.empty(lib.meld_knn16_list_scratch_bytes(N), dtype=torch.uint8, device=dev)
+            check(lib.meld_knn16_step_lists_direct_lead(ptr(X_s), N, d, ptr(mean_s), ptr(o.scale_info), ptr(nmax), ptr(o.Rt), ptr(seeds), ptr(o.Qn), plan.nprod,
+                                                        ptr(tmpb), ptr(scratch), ptr(step_list), n_tiles, ptr(step_cnt), int(plan.partial_in_search), st),
+                  "meld_knn16_step_lists_direct")
+            del scratch
+        else:
+            sb = plan.seeded_bounds
+            lb2 = torch.empty(lib.meld_knn16_bounds_bytes(N, a.q_count), dtype=torch.uint8, device=dev)
+            check((lib.meld_knn16_bounds_from_spheres if plan.bounds == "bounds_from_spheres" else lib.meld_knn16_bounds)(
+                ptr(X_s), N, d, ptr(mean_s), ptr(o.scale_info), ptr(nmax), ptr(o.Rt), a.q_begin, a.q_count, ptr(seeds) if sb else None,
+                ptr(o.Qn) if sb else None, plan.nprod, ptr(tmpb), ptr(lb2), st), "meld_knn16_bounds")
+            if plan.lists == "table":
+                # the tiles a block can rule out at its start thresholds, written down once (the count is the block's work)
+                step_list = torch.empty(n_blocks * n_tiles, dtype=torch.int32, device=dev)
+                step_cnt = torch.empty(n_blocks, dtype=torch.int32, device=dev)
+                check(lib.meld_knn16_step_lists(ptr(lb2), ptr(seeds), N, d, a.q_count, plan.nprod, ptr(nmax), ptr(o.scale_info), a.q_begin,
+                                                ptr(step_list), n_tiles, ptr(step_cnt), st), "meld_knn16_step_lists")
+        work = step_cnt
+        if plan.block_order == "work":
+            # longest query blocks first (the dispatch follows the block index): see meld_knn16_block_work
+            work = torch.empty(n_blocks, dtype=torch.int32, device=dev)
+            check(lib.meld_knn16_block_work(ptr(lb2), ptr(seeds), N, d, a.q_count, plan.nprod, ptr(nmax), ptr(o.scale_info), ptr(work), st), "meld_knn16_block_work")
+        block_order = torch.argsort(work, descending=True, stable=True).to(torch.int32) if plan.block_order != "none" else None
+        a.tm.stop("bounds")
+        return lb2, step_list, step_cnt, block_order
+
+    def _search16(self, a, plan, o, c, ksel, seeds, rfac, lists):
+        """The first pass: the partial filter where the plan has one (the search then stages whole tiles for the quarter of the
+        pairs that survive), then the search itself, over ``plan.main_slices`` slices of the references."""
+        lib, st, dev, d, q_count, q_pad, cap = self.lib, _stream(), a.X.device, a.d, a.q_count, o.q_pad, c.cap
+        lb2, step_list, step_cnt, block_order = lists
+        q0 = 0 if a.cross else a.q_begin
+        tiles_b = c.tiles_done
+        if plan.two_pass:
+            with _EventSpan("knn_filter", N=a.N, d=d, q=q_count):
+                check(lib.meld_knn16_partial_filter(ptr(o.Q), ptr(o.Qn), ptr(o.Rt), ptr(o.scale_info), ptr(c.nmax), d, q_count, ptr(seeds), ptr(step_list),
+                                                    ptr(step_cnt), o.n_tiles, ptr(step_cnt), ptr(c.tiles_done), ptr(block_order), st), "meld_knn16_partial_filter")
+                if block_order is not None:  # (longest blocks first, by what is left of them)
+                    block_order = torch.argsort(step_cnt, descending=True, stable=True).to(torch.int32)
+            tiles_b = c.tiles_done[1:]  # (the search counts the pairs it computes, and its blocks, behind the filter's)
+            a.tm.stop("knn_filter")
+        S = plan.main_slices
+        with _EventSpan("knn_topk", N=a.N, d=d, q=q_count):
+            if S > 1:  # every slice with its own candidate rows, merged afterwards
+                out = (torch.empty(S * q_pad * cap, dtype=torch.int32, device=dev), torch.empty(S * q_pad * cap, dtype=torch.float32, device=dev),
+                       torch.empty(S * q_pad, dtype=torch.int32, device=dev), torch.full((S, q_pad), float("inf"), dtype=torch.float32, device=dev))
+            else:
+                out = (c.idx, c.d2, c.cnt, c.thr)
+            if step_list is not None:
+                check(lib.meld_knn16_topk_listed_partial(ptr(o.Q), ptr(o.Qn), ptr(o.Rt), ptr(o.scale_info), a.NR, d, q_count, ksel, ptr(step_list), ptr(step_cnt),
+                                                         o.n_tiles, ptr(c.nmax), q0, ptr(seeds), plan.knn_cut, rfac, *map(ptr, out), ptr(tiles_b), ptr(block_order),
+                                                         S, int(plan.partial_in_search), st), "meld_knn16_topk_listed")
+            else:
+                check(lib.meld_knn16_topk(ptr(o.Q), ptr(o.Qn), ptr(o.Rt), ptr(o.scale_info), a.NR, d, q_count, ksel, plan.nprod, S, ptr(lb2), ptr(c.nmax), q0,
+                                          ptr(seeds), plan.knn_cut, rfac, *map(ptr, out), ptr(c.tiles_done), ptr(block_order), st), "meld_knn16_topk")
+            if S > 1:
+                check(lib.meld_knn16_merge_slices(*map(ptr, out[:3]), q_count, ksel, S, ptr(c.idx), ptr(c.d2), ptr(c.cnt), st), "meld_knn16_merge_slices")
+                c.thr.copy_(out[3].amin(0))  # the merged row holds every reference below the smallest slice threshold
+            del out
+            # the search is the one long launch of the build (26 of 45 ms at 1M cells) and the host has nothing to do until its
+            # results are refined: work that does not depend on the graph (fit_transform's label factorisation: a host-blocking
+            # copy + a few small launches on a side stream) is started here
+            while _WHILE_SEARCHING:
+                _WHILE_SEARCHING.pop()()
+        del o.Q
+
+    def _refine(self, a, c, ksel):
+        """Exact refinement + alpha-decay kernel of every candidate row; rows the first pass could not certify searched again with
+        the full hi/lo split (a few % of the rows) where the plan has that stage; then ONE read-back of the scalars the host
+        wants here (each one is an idle gap of the GPU of ~50 us: nothing is queued behind it): rows still flagged, kept
+        entries, (wave, tile) pairs the first pass computed."""
+        lib, st, dev, q_count = self.lib, _stream(), a.X.device, a.q_count
+        r = SimpleNamespace(plan=c.plan, cands=c)
+        max_rank = 0 if a.knn_max is None else int(a.knn_max) + 1  # (self counted, as graphtools counts it)
+        r.bw = torch.empty(q_count, dtype=torch.float64, device=dev)
+        r.cand_val = torch.empty(q_count * ksel, dtype=torch.float64, device=dev)
+        r.keep_cnt = torch.empty(q_count, dtype=torch.int32, device=dev)
+        r.flag_rows = torch.empty(q_count, dtype=torch.int32, device=dev)
         n_flag = torch.zeros(1, dtype=torch.int32, device=dev)
-        nmax_used = nmax
-        if force_fallback:  # test hook: an infinite error bound flags every row
+        nmax_used = c.nmax
+        if a.force_fallback:  # test hook: an infinite error bound flags every row
             nmax_used = torch.full((1,), float("inf"), dtype=torch.float32, device=dev)
-        if opt("MELD_REFINE_STATS") and bw_fixed is None:  # (development: how many candidate rows the refinement gathers per row)
-            c2 = cand_d2.view(-1, cap)[:q_count].to(torch.float64)
-            cn = cand_cnt[:q_count].clamp(max=ksel)
-            E_ = float(err_coef) * nmax.to(torch.float64) + float(err_lin) * torch.sqrt(norm2[q_begin : q_begin + q_count].to(torch.float64) * nmax.to(torch.float64))
-            rf_ = max((1.0 if math.isinf(decay) else float((-math.log(thresh)) ** (1.0 / decay))) * float(bw_scale), 1.0)
-            skip_ = rf_ * rf_ * (c2[:, min(knn, cap - 1)] + E_) + E_
-            g_ = ((c2 <= skip_[:, None]) & (torch.arange(cap, device=dev)[None, :] < cn[:, None])).sum(1).to(torch.float64)
-            print("[refine] rows %d  listed: mean %.1f  gathered: mean %.1f  median %.0f  p90 %.0f  p99 %.0f  max %.0f" % (
-                q_count, cn.to(torch.float64).mean(), g_.mean(), g_.median(), torch.quantile(g_, 0.9), torch.quantile(g_, 0.99), g_.max()), file=sys.stderr)
         check(
             lib.meld_knn_refine(
-                ptr(X), N, d, q_begin, q_count, ptr(cand_idx), ptr(cand_d2), ptr(cand_cnt), ptr(cand_thr), ksel, cap, knn, float(decay),
-                float(thresh), ptr(nmax_used), float(err_coef), ptr(norm2), float(err_lin), ptr(bw), ptr(cand_val), ptr(keep_cnt),
-                ptr(flag_rows), ptr(n_flag), None, 0, None, float(bw_scale), ptr(bw_fixed), max_rank, st,
+                ptr(a.X), a.N, a.d, a.q_begin, q_count, ptr(c.idx), ptr(c.d2), ptr(c.cnt), ptr(c.thr), ksel, c.cap, a.knn, float(a.decay),
+                float(a.thresh), ptr(nmax_used), float(c.err_coef), ptr(c.norm2), float(c.err_lin), ptr(r.bw), ptr(r.cand_val), ptr(r.keep_cnt),
+                ptr(r.flag_rows), ptr(n_flag), None, 0, None, float(a.bw_scale), ptr(a.bw_fixed), max_rank, st,
             ),
             "meld_knn_refine",
         )
-        n_flag_h = int(n_flag.item())
-        n_flag_stage1 = n_flag_h
-        tm.stop("refine")
-
-        # second search stage: rows the reduced-precision pass could not certify are searched again with
-        # the full hi/lo split (a few % of the rows); only what that cannot certify either goes to the
-        # exact sweep
-        if research is not None and n_flag_h > 0 and not force_fallback:
-            rows2 = torch.sort(flag_rows[:n_flag_h]).values.contiguous()
-            KB, BQ2 = research["KB"], research["BQ"]
-            q2_pad = ((n_flag_h + BQ2 - 1) // BQ2) * BQ2
-            Q2 = torch.empty(q2_pad * lib.meld_knn16_query_bytes(d), dtype=torch.uint8, device=dev)
-            Qn2 = torch.empty(q2_pad, dtype=torch.float32, device=dev)
-            check(lib.meld_knn16_prepare_rows(ptr(X_search), N, d, ptr(mean_search), ptr(research["scale_info"]), q_begin, ptr(rows2), n_flag_h, ptr(Q2), ptr(Qn2), st), "meld_knn16_prepare_rows")
-            # few queries: cut the references into slices so that the re-search fills the chip
-            n_blocks2 = q2_pad // BQ2
-            resident = lib.meld_knn16_resident_blocks(d, 3)
-            if resident < 0:
-                check(resident, "meld_knn16_resident_blocks")
-            n_slices = int(max(1, min(lib.meld_knn16_max_slices(ksel), 2 * resident // max(n_blocks2, 1), n_tiles)))
-            # Start the thresholds of the re-search at a bound instead of +inf: the first pass found ksel
-            # references with approximate d2 <= tau, so the true ksel-th distance is <= tau + E1 and its
-            # full-precision approximation <= tau + E1 + E3 -- nothing above that can enter the list.
-            # (Without it every slice selects from scratch: 19k appends per query at 1M cells.)
-            thr2 = torch.empty(q2_pad, dtype=torch.float32, device=dev)
-            check(lib.meld_knn16_research_thresholds(ptr(rows2), n_flag_h, q_begin, ptr(cand_cnt), ptr(cand_d2), cap, ksel, ptr(norm2), ptr(nmax),
-                                                     float(err_coef), float(err_lin), float(lib.meld_knn16_error_coef(3, d)),
-                                                     ptr(research["scale_info"]), ptr(thr2), st), "meld_knn16_research_thresholds")
-            c2_idx = torch.empty(n_slices * q2_pad * cap, dtype=torch.int32, device=dev)
-            c2_d2 = torch.empty(n_slices * q2_pad * cap, dtype=torch.float32, device=dev)
-            c2_cnt = torch.empty(n_slices * q2_pad, dtype=torch.int32, device=dev)
-            with _EventSpan("knn_topk_stage2", N=N, d=d, q=n_flag_h):
-                check(lib.meld_knn16_topk(ptr(Q2), ptr(Qn2), ptr(research["Rt"]), ptr(research["scale_info"]), NR, d, n_flag_h, ksel, 3, n_slices, None, ptr(nmax), 0, ptr(thr2), 0, 1.0, ptr(c2_idx), ptr(c2_d2), ptr(c2_cnt), None, None, None, st), "meld_knn16_topk(stage 2)")
-                if n_slices > 1:
-                    m_idx = torch.empty(q2_pad * cap, dtype=torch.int32, device=dev)
-                    m_d2 = torch.empty(q2_pad * cap, dtype=torch.float32, device=dev)
-                    m_cnt = torch.empty(q2_pad, dtype=torch.int32, device=dev)
-                    check(lib.meld_knn16_merge_slices(ptr(c2_idx), ptr(c2_d2), ptr(c2_cnt), n_flag_h, ksel, n_slices, ptr(m_idx), ptr(m_d2), ptr(m_cnt), st), "meld_knn16_merge_slices")
-                    c2_idx, c2_d2, c2_cnt = m_idx, m_d2, m_cnt
-            n_flag.zero_()
-            check(
-                lib.meld_knn_refine(
-                    ptr(X), N, d, q_begin, n_flag_h, ptr(c2_idx), ptr(c2_d2), ptr(c2_cnt), None, ksel, cap, knn, float(decay),
-                    float(thresh), ptr(nmax), float(lib.meld_knn16_error_coef(3, d)), None, 0.0, ptr(bw), ptr(cand_val), ptr(keep_cnt),
-                    ptr(flag_rows), ptr(n_flag), ptr(rows2), cap, ptr(cand_idx), float(bw_scale), ptr(bw_fixed), max_rank, st,
-                ),
-                "meld_knn_refine(stage 2)",
-            )
-            del Q2, c2_idx, c2_d2, c2_cnt
-            n_flag_stale = True
-            tm.stop("knn_stage2")
-        else:
-            n_flag_stale = False
-        research = None
-        Rt = None
-        keep_off = _scan_i32(lib, keep_cnt, st)
-        # ONE read-back for the three scalars the host wants here (each one is an idle gap of the GPU of ~50 us: nothing is queued
-        # behind it): rows still flagged after the second stage, kept entries, (wave, tile) pairs the first pass computed
-        heads = [n_flag[0].to(torch.int64), keep_off[q_count]] + ([tiles_done[0], tiles_done[2] if used_two_phase else tiles_done[1], tiles_done[1]] if tiles_done is not None else [])
+        r.n_flag = r.n_flag_stage1 = int(n_flag.item())
+        a.tm.stop("refine")
+        stage2 = c.research is not None and r.n_flag > 0 and not a.force_fallback
+        if stage2:
+            self._stage2(a, c, r, ksel, n_flag, max_rank)
+        c.research = None
+        r.keep_off = _scan_i32(lib, r.keep_cnt, st)
+        td, p = c.tiles_done, c.plan
+        heads = [n_flag[0].to(torch.int64), r.keep_off[q_count]] + ([td[0], td[2] if p.two_pass else td[1], td[1]] if td is not None else [])
         heads_h = torch.stack(heads).tolist()
-        if n_flag_stale:
-            n_flag_h = int(heads_h[0])
-        m_main = int(heads_h[1])
-        tiles_done_h = int(heads_h[2]) if tiles_done is not None else None
-        blocks_on_h = int(heads_h[3]) if tiles_done is not None and X_search is not X else None
-        pairs_kept_h = int(heads_h[4]) if tiles_done is not None and used_two_phase else None  # (wave, tile) pairs the filter pass left to the search
-        if pairs_kept_h is not None and lib.meld_knn16_kblocks(d) > 7:
-            blocks_on_h = 2 * pairs_kept_h  # (beyond seven K blocks the search behind the filter has no test of its own: both blocks of every pair it is handed)
+        if stage2:
+            r.n_flag = int(heads_h[0])
+        r.m_main = int(heads_h[1])
+        r.tiles_done_h = int(heads_h[2]) if td is not None else None
+        r.blocks_on_h = int(heads_h[3]) if td is not None and p.frame else None
+        r.pairs_kept_h = int(heads_h[4]) if td is not None and p.two_pass else None  # (wave, tile) pairs the filter pass left to the search
+        if r.pairs_kept_h is not None and lib.meld_knn16_kblocks(a.d) > 7:
+            r.blocks_on_h = 2 * r.pairs_kept_h  # (beyond seven K blocks the search behind the filter has no test of its own: both blocks of every pair it is handed)
+        return r
 
-        # Many uncertified rows with a short candidate list (dense low-dimensional data: more than ksel cells
-        # inside the radius inflated by the search-error allowance): search once more with the longest list
-        # instead of sweeping them one by one (1M cells in the plane, knn = 15: 292k rows through the sweep at
-        # ksel = 64, 0.63 s; none at ksel = 128, 32 ms).  Same graph either way.
-        if (n_flag_h > max(1024, q_count // 100) and ksel < 128 and search == "f16x3" and not force_fallback
-                and opt("MELD_KNN_RETRY", "1") != "0"):
-            # (comm is NOT forwarded on purpose: only the ranks that need the retry take it, so it must not issue collectives
-            # -- the shared-spheres all-gather of the first try is skipped, every rank computes all spheres itself)
-            out = self.directed_kernel_coo(X, q_begin, q_count, knn, decay, thresh, 128, tm=tm, force_fallback=False, n_refs=n_refs,
-                                           assemble=assemble, bw_scale=bw_scale, bw_fixed=bw_fixed, col_stats=col_stats, knn_max=knn_max, symm=symm,
-                                           count_rows_ge=count_rows_ge, frame_axes=frame_axes)
-            out[3]["ksel_retry_from"] = int(ksel)
-            out[3]["n_flagged_rows_first_try"] = int(n_flag_h)
-            return out
+    def _stage2(self, a, c, r, ksel, n_flag, max_rank):
+        """The flagged rows searched again with the full hi/lo split; only what that cannot certify either goes to the exact sweep."""
+        lib, st, dev, d, cap, o = self.lib, _stream(), a.X.device, a.d, c.cap, c.research
+        n_flag_h = r.n_flag
+        rows2 = torch.sort(r.flag_rows[:n_flag_h]).values.contiguous()
+        q2_pad = ((n_flag_h + o.BQ - 1) // o.BQ) * o.BQ
+        Q2 = torch.empty(q2_pad * lib.meld_knn16_query_bytes(d), dtype=torch.uint8, device=dev)
+        Qn2 = torch.empty(q2_pad, dtype=torch.float32, device=dev)
+        check(lib.meld_knn16_prepare_rows(ptr(o.X_s), a.N, d, ptr(o.mean_s), ptr(o.scale_info), a.q_begin, ptr(rows2), n_flag_h, ptr(Q2), ptr(Qn2), st), "meld_knn16_prepare_rows")
+        # few queries: cut the references into slices so that the re-search fills the chip
+        n_blocks2 = q2_pad // o.BQ
+        resident = lib.meld_knn16_resident_blocks(d, 3)
+        if resident < 0:
+            check(resident, "meld_knn16_resident_blocks")
+        n_slices = int(max(1, min(lib.meld_knn16_max_slices(ksel), 2 * resident // max(n_blocks2, 1), o.n_tiles)))
+        # Start the thresholds of the re-search at a bound instead of +inf: the first pass found ksel references with approximate
+        # d2 <= tau, so the true ksel-th distance is <= tau + E1 and its full-precision approximation <= tau + E1 + E3 -- nothing
+        # above that can enter the list.  (Without it every slice selects from scratch: 19k appends per query at 1M cells.)
+        thr2 = torch.empty(q2_pad, dtype=torch.float32, device=dev)
+        check(lib.meld_knn16_research_thresholds(ptr(rows2), n_flag_h, a.q_begin, ptr(c.cnt), ptr(c.d2), cap, ksel, ptr(c.norm2), ptr(c.nmax),
+                                                 float(c.err_coef), float(c.err_lin), float(lib.meld_knn16_error_coef(3, d)),
+                                                 ptr(o.scale_info), ptr(thr2), st), "meld_knn16_research_thresholds")
+        c2_idx = torch.empty(n_slices * q2_pad * cap, dtype=torch.int32, device=dev)
+        c2_d2 = torch.empty(n_slices * q2_pad * cap, dtype=torch.float32, device=dev)
+        c2_cnt = torch.empty(n_slices * q2_pad, dtype=torch.int32, device=dev)
+        with _EventSpan("knn_topk_stage2", N=a.N, d=d, q=n_flag_h):
+            check(lib.meld_knn16_topk(ptr(Q2), ptr(Qn2), ptr(o.Rt), ptr(o.scale_info), a.NR, d, n_flag_h, ksel, 3, n_slices, None, ptr(c.nmax), 0, ptr(thr2), 0, 1.0,
+                                      ptr(c2_idx), ptr(c2_d2), ptr(c2_cnt), None, None, None, st), "meld_knn16_topk(stage 2)")
+            if n_slices > 1:
+                m_idx = torch.empty(q2_pad * cap, dtype=torch.int32, device=dev)
+                m_d2 = torch.empty(q2_pad * cap, dtype=torch.float32, device=dev)
+                m_cnt = torch.empty(q2_pad, dtype=torch.int32, device=dev)
+                check(lib.meld_knn16_merge_slices(ptr(c2_idx), ptr(c2_d2), ptr(c2_cnt), n_flag_h, ksel, n_slices, ptr(m_idx), ptr(m_d2), ptr(m_cnt), st), "meld_knn16_merge_slices")
+                c2_idx, c2_d2, c2_cnt = m_idx, m_d2, m_cnt
+        n_flag.zero_()
+        check(
+            lib.meld_knn_refine(
+                ptr(a.X), a.N, d, a.q_begin, n_flag_h, ptr(c2_idx), ptr(c2_d2), ptr(c2_cnt), None, ksel, cap, a.knn, float(a.decay),
+                float(a.thresh), ptr(c.nmax), float(lib.meld_knn16_error_coef(3, d)), None, 0.0, ptr(r.bw), ptr(r.cand_val), ptr(r.keep_cnt),
+                ptr(r.flag_rows), ptr(n_flag), ptr(rows2), cap, ptr(c.idx), float(a.bw_scale), ptr(a.bw_fixed), max_rank, st,
+            ),
+            "meld_knn_refine(stage 2)",
+        )
+        a.tm.stop("knn_stage2")
 
-        # exact sweep for rows the candidate list could not certify
-        knn_chk = knn if bw_fixed is None else 2**31 - 1  # (a given bandwidth is not verified against the neighbour count)
-        n_rebandwidth = 0
-        fb_total = 0
-        fb_off = fb_col = fb_val = None
+    def _exact_sweep(self, a, r, count_rows_ge):
+        """Exact sweep of the rows the candidate lists could not certify (their bandwidth recomputed where a list missed one of
+        the knn nearest cells, knn_max applied to the swept rows), and the count of rows with at least ``count_rows_ge`` cells."""
+        lib, st, dev, q_count, n_flag_h = self.lib, _stream(), a.X.device, a.q_count, r.n_flag
+        knn_chk = a.knn if a.bw_fixed is None else 2**31 - 1  # (a given bandwidth is not verified against the neighbour count)
+        s = SimpleNamespace(n_rebandwidth=0, fb_total=0, fb_off=None, fb_col=None, fb_val=None, fb_cnt=None, rows_at_least=None)
         if n_flag_h > 0:
-            flag_rows = torch.sort(flag_rows[:n_flag_h]).values.contiguous()  # deterministic order
+            r.flag_rows = flag_rows = torch.sort(r.flag_rows[:n_flag_h]).values.contiguous()  # deterministic order
             fb_cnt = torch.empty(n_flag_h, dtype=torch.int32, device=dev)
             err = torch.zeros(1, dtype=torch.int32, device=dev)
             cursor = torch.zeros(n_flag_h, dtype=torch.int32, device=dev)  # count pass: references closer than bw
-            check(
-                lib.meld_knn_radius_exact(
-                    ptr(X), NR, d, q_begin, ptr(flag_rows), n_flag_h, ptr(bw), knn_chk, float(decay), float(thresh), 0,
-                    ptr(fb_cnt), None, ptr(cursor), None, None, ptr(err), float(bw_scale), st,
-                ),
-                "meld_knn_radius_exact(count)",
-            )
+
+            def sweep(fill, what, fb_cnt=None, fb_off=None, fb_col=None, fb_val=None, err=None):
+                check(lib.meld_knn_radius_exact(ptr(a.X), a.NR, a.d, a.q_begin, ptr(flag_rows), n_flag_h, ptr(r.bw), knn_chk, float(a.decay), float(a.thresh), fill,
+                                                ptr(fb_cnt), ptr(fb_off), ptr(cursor), ptr(fb_col), ptr(fb_val), ptr(err), float(a.bw_scale), st), what)
+
+            sweep(0, "meld_knn_radius_exact(count)", fb_cnt=fb_cnt, err=err)
             if int(err.item()) != 0:
-                # rows whose candidate list missed one of their knn nearest cells (marked fb_cnt = -1: more than knn
-                # references are strictly closer than the bandwidth the list implied): their bandwidth is recomputed
-                # exactly over all references -- a rare library path (fp64 screen + direct differences) -- and the
-                # sweep is counted again (graphtools re-searches such rows with more neighbours)
+                # rows whose candidate list missed one of their knn nearest cells (marked fb_cnt = -1: more than knn references are
+                # strictly closer than the bandwidth the list implied): their bandwidth is recomputed exactly over all references --
+                # a rare library path (fp64 screen + direct differences) -- and the sweep is counted again (graphtools re-searches
+                # such rows with more neighbours)
                 bad = torch.nonzero(fb_cnt < 0).reshape(-1)
                 rows_bad = flag_rows[bad].to(torch.int64)
-                bw[rows_bad] = _exact_bandwidth(X, q_begin + rows_bad, knn, n_refs=NR)
+                r.bw[rows_bad] = _exact_bandwidth(a.X, a.q_begin + rows_bad, a.knn, n_refs=a.NR)
                 fb_cnt.zero_()
                 cursor.zero_()
                 err.zero_()
-                check(
-                    lib.meld_knn_radius_exact(
-                        ptr(X), NR, d, q_begin, ptr(flag_rows), n_flag_h, ptr(bw), knn_chk, float(decay), float(thresh), 0,
-                        ptr(fb_cnt), None, ptr(cursor), None, None, ptr(err), float(bw_scale), st,
-                    ),
-                    "meld_knn_radius_exact(recount)",
-                )
+                sweep(0, "meld_knn_radius_exact(recount)", fb_cnt=fb_cnt, err=err)
                 if int(err.item()) != 0:
                     raise NotImplementedError(
                         "degenerate neighbourhoods: the exact sweep could not settle the bandwidth of {} rows".format(int((fb_cnt < 0).sum())))
-                n_rebandwidth = int(bad.shape[0])
+                s.n_rebandwidth = int(bad.shape[0])
             fb_off = _scan_i32(lib, fb_cnt, st)
             fb_total = int(fb_off[n_flag_h].item())
             # (a radius that covers most of the data -- small decay with a small thresh -- makes the graph effectively dense: say so
             # instead of failing inside an allocation; the reference's scipy matrices would be as large)
-            need = 12 * fb_total + 32 * (m_main + fb_total)
+            need = 12 * fb_total + 32 * (r.m_main + fb_total)
             if need > torch.cuda.get_device_properties(dev).total_memory:
                 raise MemoryError(
                     "the kernel radius covers {:.3g} neighbours per cell on average: the graph would hold {:.3g} entries ({:.0f} GB to "
-                    "assemble) -- raise decay or thresh".format((m_main + fb_total) / max(q_count, 1), float(m_main + fb_total), need / 1e9))
+                    "assemble) -- raise decay or thresh".format((r.m_main + fb_total) / max(q_count, 1), float(r.m_main + fb_total), need / 1e9))
             fb_col = torch.empty(max(fb_total, 1), dtype=torch.int32, device=dev)
             fb_val = torch.empty(max(fb_total, 1), dtype=torch.float64, device=dev)
-            check(  # (the count pass left the cursors at zero)
-                lib.meld_knn_radius_exact(
-                    ptr(X), NR, d, q_begin, ptr(flag_rows), n_flag_h, ptr(bw), knn_chk, float(decay), float(thresh), 1,
-                    None, ptr(fb_off), ptr(cursor), ptr(fb_col), ptr(fb_val), None, float(bw_scale), st,
-                ),
-                "meld_knn_radius_exact(fill)",
-            )
-            if knn_max is not None and fb_total > 0 and int(fb_cnt.max()) > int(knn_max):
+            sweep(1, "meld_knn_radius_exact(fill)", fb_off=fb_off, fb_col=fb_col, fb_val=fb_val)  # (the count pass left the cursors at zero)
+            if a.knn_max is not None and fb_total > 0 and int(fb_cnt.max()) > int(a.knn_max):
                 # knn_max on the rows the sweep filled (everything inside the radius, unranked): keep the knn_max largest kernel
                 # values of a row (= its nearest cells; ties by column) -- a rare path, a few library sorts over the swept entries
                 rows_e = torch.repeat_interleave(torch.arange(n_flag_h, device=dev), fb_cnt.to(torch.int64))
@@ -1079,69 +1020,61 @@ class HipOps:
                 o = o[torch.argsort(-fb_val[:fb_total][o], stable=True)]
                 o = o[torch.argsort(rows_e[o], stable=True)]
                 rank = torch.arange(fb_total, device=dev) - fb_off[:n_flag_h][rows_e[o]]
-                keep = o[rank < int(knn_max)]
+                keep = o[rank < int(a.knn_max)]
                 keep = keep[torch.argsort(rows_e[keep], stable=True)]
                 fb_col, fb_val = fb_col[keep].contiguous(), fb_val[keep].contiguous()
-                fb_cnt = torch.clamp(fb_cnt, max=int(knn_max))
+                fb_cnt = torch.clamp(fb_cnt, max=int(a.knn_max))
                 fb_off = _scan_i32(lib, fb_cnt, st)
                 fb_total = int(fb_off[n_flag_h].item())
-        tm.stop("radius_exact")
-        rows_at_least = None
+            s.fb_total, s.fb_off, s.fb_col, s.fb_val, s.fb_cnt = fb_total, fb_off, fb_col, fb_val, fb_cnt
+        a.tm.stop("radius_exact")
         if count_rows_ge is not None:
-            tot = keep_cnt.to(torch.int64)
-            if n_flag_h > 0 and fb_total > 0:
+            tot = r.keep_cnt.to(torch.int64)
+            if n_flag_h > 0 and s.fb_total > 0:
                 tot = tot.clone()
-                tot[flag_rows[:n_flag_h].to(torch.int64)] = fb_cnt.to(torch.int64)
-            rows_at_least = int(((tot + 1) >= int(count_rows_ge)).sum())  # (+ 1: the cell itself, K_ii = 1 is carried analytically)
+                tot[r.flag_rows[:n_flag_h].to(torch.int64)] = s.fb_cnt.to(torch.int64)
+            s.rows_at_least = int(((tot + 1) >= int(count_rows_ge)).sum())  # (+ 1: the cell itself, K_ii = 1 is carried analytically)
+        return s
 
-        M = m_main + fb_total
+    def _emit(self, a, r, s, ksel, assemble, symm):
+        """The kept entries as (keys, vals) COO pairs -- or, on a single GPU with every row local, straight into the row buckets of
+        the symmetrisation (meld_coo_emit_scatter) instead of through 2 M (key, value) pairs (512 MB written and read back at 1M
+        cells).  Returns (keys, vals, assembled): assembled = (rowptr, col, val[, row sums]) of the symmetrised rows, else None."""
+        lib, st, dev, q_count, n_flag_h, c = self.lib, _stream(), a.X.device, a.q_count, r.n_flag, r.cands
+        M = r.m_main + s.fb_total
         assembled = None
-        if assemble and M > 0 and q_begin == 0 and q_count == NR and not cross and opt("MELD_ASSEMBLE", "bucket") == "bucket" \
+        if assemble and M > 0 and a.q_begin == 0 and q_count == a.NR and not a.cross and opt("MELD_ASSEMBLE", "bucket") == "bucket" \
                 and opt("MELD_ASSEMBLE_FUSED", "1") != "0":
-            # single GPU, every row local: the kept candidates go straight into the row buckets of the symmetrisation
-            # (meld_coo_emit_scatter) instead of through 2 M (key, value) pairs -- 512 MB written and read back at 1M cells
             B = int(lib.meld_csr_bucket_slots())
             if ksel <= B and q_count * B * 12 <= torch.cuda.mem_get_info(dev)[0] // 4:
-                cursor = keep_cnt.clone()
-                if n_flag_h > 0 and fb_total > 0:
-                    cursor[flag_rows[:n_flag_h].to(torch.int64)] = fb_cnt
+                cursor = r.keep_cnt.clone()
+                if n_flag_h > 0 and s.fb_total > 0:
+                    cursor[r.flag_rows[:n_flag_h].to(torch.int64)] = s.fb_cnt
                 tcol = torch.empty(q_count * B, dtype=torch.int32, device=dev)
                 tval = torch.empty(q_count * B, dtype=torch.float64, device=dev)
-                check(lib.meld_coo_emit_scatter(q_count, ptr(cand_idx), ptr(cand_val), ksel, cap, ptr(keep_cnt), ptr(flag_rows), n_flag_h,
-                                                ptr(fb_off), ptr(fb_col), ptr(fb_val), fb_total, ptr(cursor), ptr(tcol), ptr(tval), st),
+                check(lib.meld_coo_emit_scatter(q_count, ptr(c.idx), ptr(r.cand_val), ksel, c.cap, ptr(r.keep_cnt), ptr(r.flag_rows), n_flag_h,
+                                                ptr(s.fb_off), ptr(s.fb_col), ptr(s.fb_val), s.fb_total, ptr(cursor), ptr(tcol), ptr(tval), st),
                       "meld_coo_emit_scatter")
-                tm.stop("coo_emit")
+                a.tm.stop("coo_emit")
                 assembled = self._finish_buckets(cursor, tcol, tval, q_count, sums_diag=1.0, symm=symm)  # None: a bucket overflowed / a column thrice
                 if assembled is not None and self.last_row_sums is not None:
                     assembled = assembled + (self.last_row_sums[1],)  # (kernel row sums incl. the unit diagonal)
-                tm.stop("symmetrize")
+                a.tm.stop("symmetrize")
                 del cursor, tcol, tval
         keys = vals = None
         if assembled is None:
             keys = torch.empty(2 * M, dtype=torch.int64, device=dev)
             vals = torch.empty(2 * M, dtype=torch.float64, device=dev)
-        if M > 0 and assembled is None:
-            check(
-                lib.meld_coo_emit(
-                    q_begin, q_count, ptr(cand_idx), ptr(cand_val), ptr(cand_cnt), ksel, cap, ptr(keep_off), ptr(flag_rows),
-                    n_flag_h, ptr(fb_off), ptr(fb_col), ptr(fb_val), m_main, M, ptr(keys), ptr(vals), st,
-                ),
-                "meld_coo_emit",
-            )
-        tm.stop("coo_emit")
-        nprod_used = nprod if search == "f16x3" else self.nprod
-        info = dict(ksel=int(ksel), KP=int(KP), search=search, nprod=nprod_used, n_flagged_rows=n_flag_h,
-                    # which of the search options (constructor arguments / MELD_KNN_* ablation switches) were in effect
-                    prune=bool(used_prune), radius_cut=bool(cand_thr is not None), seed=bool(used_seed), seeded_bounds=bool(used_seeded_bounds), block_order=bool(used_block_order), step_lists=bool(used_step_lists), principal_frame=bool(X_search is not X), two_phase=bool(used_two_phase), seed_side=int(opt("MELD_KNN_SEED_SIDE", "0")),
-                    n_rows_bandwidth_recomputed=n_rebandwidth,
-                    n_researched_rows=n_flag_stage1 if search == 'f16x3' and nprod_used == 1 else 0, nnz_directed=M,
-                    # (wave, tile) pairs the first search pass computed (all of them without pruning)
-                    wave_tiles_done=tiles_done_h, blocks_past_partial_test=blocks_on_h, pairs_past_filter=pairs_kept_h)
-        if rows_at_least is not None:
-            info["rows_with_at_least"] = rows_at_least
-        if assembled is not None:
-            info["assembled"] = assembled  # (rowptr, col, val) of the symmetrised rows: the caller skips assemble_rows
-        return keys, vals, bw, info
+            if M > 0:
+                check(
+                    lib.meld_coo_emit(
+                        a.q_begin, q_count, ptr(c.idx), ptr(r.cand_val), ptr(c.cnt), ksel, c.cap, ptr(r.keep_off), ptr(r.flag_rows),
+                        n_flag_h, ptr(s.fb_off), ptr(s.fb_col), ptr(s.fb_val), r.m_main, M, ptr(keys), ptr(vals), st,
+                    ),
+                    "meld_coo_emit",
+                )
+        a.tm.stop("coo_emit")
+        return keys, vals, assembled
 
     # ---- A4: (K + K^T)/2 rows [row_begin, row_begin + n_rows) from unsorted COO ---------------------
     def sort_pairs(self, keys, vals, N):

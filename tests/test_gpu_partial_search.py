@@ -149,3 +149,32 @@ def test_repeated_builds_agree_with_an_odd_number_of_k_blocks(d, monkeypatch):
     for _ in range(25):
         assert torch.equal(bandwidths("1"), ref)
         assert torch.equal(bandwidths("0"), ref)
+
+
+@pytest.mark.parametrize("case", ["frame", "frame_declined", "shard", "low_d", "small", "cross"])
+def test_build_follows_its_plan(case):
+    """What a real build reports in ``info`` is the route meld_amd.knn_plan gives for the same inputs (tests/test_knn_plan.py pins
+    the routes without a GPU)."""
+    from meld_amd.graph import HipOps
+    from meld_amd.knn_plan import plan_knn_search, search_nprod
+    from meld_amd.reorder import locality_permutation
+
+    N, d, q_begin, q_count, kw = {"frame": (33555, 32, 0, 33555, {}), "frame_declined": (33555, 32, 0, 33555, {}),
+                                  "shard": (33555, 32, 8192, 16384, {}), "low_d": (20000, 4, 0, 20000, {}),
+                                  "small": (9000, 20, 0, 9000, {}), "cross": (33555, 32, 20000, 13555, {"n_refs": 20000})}[case]
+    X = np.random.default_rng(11).normal(size=(N, d)) if case == "frame_declined" else _cells(N, d, 11)
+    Xd = torch.from_numpy(np.ascontiguousarray(X)).cuda()
+    Xd = Xd.index_select(0, locality_permutation(Xd)).contiguous()
+    ops = HipOps()
+    keys, vals, bw, info = ops.directed_kernel_coo(Xd, q_begin, q_count, 5, 40, 1e-2, 64, **kw)
+    p = plan_knn_search(ops.lib, N, d, q_begin, q_count, 5, info["ksel"], options=ops, cross="n_refs" in kw,
+                        resident=ops.lib.meld_knn16_resident_blocks(d, search_nprod(ops.nprod, d)))
+    if case == "frame_declined":  # (the leading coordinates of isotropic noise carry too little of the variance)
+        assert p.frame and not info["principal_frame"]
+        p = p.without_frame()
+    got = {k: info[k] for k in ("search", "nprod", "prune", "radius_cut", "seed", "seeded_bounds", "block_order", "step_lists", "principal_frame",
+                                "two_phase")}
+    assert got == dict(search=p.search, nprod=p.nprod, prune=p.prune, radius_cut=p.radius_cut, seed=p.seed != "none", seeded_bounds=p.seeded_bounds,
+                       block_order=p.block_order != "none", step_lists=p.lists != "none", principal_frame=p.frame, two_phase=p.two_pass)
+    assert (info["blocks_past_partial_test"] is not None) == p.partial_in_search
+    assert (info["pairs_past_filter"] is not None) == p.two_pass
