@@ -36,21 +36,14 @@
 #include <hip/hip_fp16.h>
 
 #include <algorithm>
-#include <cstdlib>
 
 namespace meld {
 
 constexpr int K16_TS = 64;         // references per LDS tile
-#ifndef K16_WG_WAVES
-#define K16_WG_WAVES 4
-#endif
-constexpr int K16_BQ = 64 * K16_WG_WAVES;        // queries per workgroup
-constexpr int K16_THREADS = 64 * K16_WG_WAVES;   // waves of 64 queries each; 2-3 workgroups resident per CU
+constexpr int K16_BQ = 256;        // queries per workgroup
+constexpr int K16_THREADS = 256;   // four waves of 64 queries each; 2-3 workgroups resident per CU
 constexpr int K16_NWAVE = K16_THREADS / 64;
 constexpr int K16_SLACK = 128;     // CAP = ksel + slack
-#ifndef K16_A_AHEAD
-#define K16_A_AHEAD 4  // A fragments of a pipeline segment requested ahead of its first MFMA (hi-only search; measured 2 -> 4: -2 %)
-#endif
 constexpr int K16_CAPMAX = 256;
 // Centroids per workgroup of the pruning-table kernel (64 per wave).  Every workgroup streams all cells of its query
 // slice past its centroids, so the tile traffic is N x d x 2 B x (tiles / centroids per workgroup): 7.9 GB at 1M cells
@@ -67,16 +60,7 @@ constexpr int K16_DMAX = 16 * 9 - 3;  // largest d (KB = 9)
 // references in which no partial value is below its row's threshold (+ |q_B|^2: the most the other blocks can take away, m_r
 // covering the fp16 rounding of r_B: see prepare16_kernel).  It pays when the leading coordinates carry the distances (principal
 // coordinates: the host rotates the cells for the search, meld_amd/graph.py; any orthonormal frame is valid).
-#ifndef K16_EE_W4
-#define K16_EE_W4 1
-#endif
-#ifndef K16_EE_PAIRS
-#define K16_EE_PAIRS 1
-#endif
 constexpr int K16_SPLIT_DA = 13;
-__host__ __device__ inline int k16_split_dims_of(int d, int KB, int enabled) {
-  return (enabled && d > K16_SPLIT_DA && d + 6 <= 16 * KB) ? K16_SPLIT_DA : 0;
-}
 // content of physical K slot c: *coord >= 0 a coordinate; *piece 0..2 the pieces of N_A, 3..5 of N_B (PLAIN: of |r|^2); both -1: zero
 __host__ __device__ inline void k16_slot(int c, int d, int dA, int* coord, int* piece) {
   *coord = -1;
@@ -334,23 +318,24 @@ struct K16Args {
 // (b) lets the scheduler keep the interleaved MFMA / vote order instead of trading it for occupancy it
 // cannot reach.  The first pass at d <= 61 fits three waves (168 registers): measured 135 ms vs 151 ms
 // with two at 1M cells -- the waves mostly wait (barrier per tile, selection slow path), so occupancy pays.
-__host__ __device__ constexpr int k16_waves(int KB, int ABL, int NPROD) {
+// The partial-test kernels (EE) at KB <= 4 fit one wave more.
+__host__ __device__ constexpr int k16_waves(int KB, int NPROD, bool EE) {
   // (the full split at KB = 6 would fit two by registers, but its three 24 KB tile buffers leave room for one workgroup per CU)
-  return (NPROD == 1 && KB <= 4 && ABL != 6) ? 3 : ((KB <= 5 || (NPROD == 1 && KB <= 8)) ? 2 : 1);
+  return ((NPROD == 1 && KB <= 4) ? 3 : ((KB <= 5 || (NPROD == 1 && KB <= 8)) ? 2 : 1)) + ((EE && KB <= 4) ? 1 : 0);
 }
 
-template <int KB, int ABL, int NPROD, bool LIST = false, bool EE = false>  // 16 KB >= d + 3; ABL: 0 = product, 2 = product + selection counters, 1 / 3 = profiling ablations (no selection / MFMAs
-                                      // only), 6 = product at two waves per SIMD where three are the default;
+template <int KB, int STATS, int NPROD, bool LIST = false, bool EE = false>  // 16 KB >= d + 3; STATS = 1: + the MELD_KNN16_STATS counters
+                                      // (an int, not a bool: the product kernels keep the mangled names tests/test_kernel_resources.py
+                                      // finds them by);
                                       // NPROD: split products (1 = hi.hi only, 3 = hi.hi + hi.lo + lo.hi)
                                       // LIST: the steps of a query block (tile + the waves that need it) come from a precomputed list
                                       // (meld_knn16_step_lists) instead of the pruning table: no per-step masks, ballots or window logic
                                       // EE (with LIST, NPROD = 1, KB >= 2, operands in the SPLIT layout): a block of 32 references is tested
                                       // on its accumulators behind K block 0 and dropped when no partial value is within reach of its row
 __global__ __launch_bounds__(K16_THREADS)
-__attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PAIRS && K16_EE_W4 && KB <= 4) ? 1 : 0),
-                                   k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PAIRS && K16_EE_W4 && KB <= 4) ? 1 : 0)))) void knn16_topk_kernel(const K16Args a) {
+__attribute__((amdgpu_waves_per_eu(k16_waves(KB, NPROD, EE), k16_waves(KB, NPROD, EE)))) void knn16_topk_kernel(const K16Args a) {
   // Arguments the scan loop needs stay in SGPRs; the cold ones (K16_COLD: compaction parameters, the outputs
-  // of the epilogue, profiling) are re-read from the kernel-argument segment where they are used -- kept live
+  // of the epilogue, the counters) are re-read from the kernel-argument segment where they are used -- kept live
   // across the loop they pushed the kernel past its 102 SGPRs, the spills went to VGPR lanes and on to
   // scratch, and the MFMA / vote interleaving fell apart (measured: 74 -> 81 ms).
   const _Float16* __restrict__ Q16 = a.Q16;
@@ -376,9 +361,9 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
   // a ring addressed by a rotating offset that is every A-fragment read.  (The earlier build kept two separate
   // arrays and the loop unrolled by two so that the pass could prove them disjoint; three arrays unrolled by three
   // spill and no longer fit the instruction cache.)  The waits are explicit instead: K16_STAGED / _BUT_LAST.
-  // PAIR (EE kernels, -DK16_EE_PAIRS): two tiles per step and barrier, two buffers of two tiles -- the steps of the partial-test
-  // pass are short, and a barrier + the control around it per 64 references is a third of what a wave spends
-  constexpr bool PAIR = EE && (K16_EE_PAIRS != 0);
+  // PAIR (EE kernels): two tiles per step and barrier, two buffers of two tiles -- the steps of the partial-test pass are short,
+  // and a barrier + the control around it per 64 references is a third of what a wave spends
+  constexpr bool PAIR = EE;
   constexpr int NBUF = PAIR ? 4 : 3;
   __shared__ __attribute__((aligned(16))) _Float16 lds_ring[NBUF * LDS_TILE_H];
   constexpr int TILE_LDS_BYTES = LDS_TILE_H * 2;
@@ -411,11 +396,9 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
   // heavy block's work in one of them) and writes its own candidate rows; meld_knn16_merge_slices combines them.  Used to
   // spread few query blocks (the re-search, a row shard, a mid-sized data set) over the whole chip.
   int sl_n_ = (int)gridDim.x;
-#ifndef K16_NO_SLN_PIN
   // (opaque to the rematerialiser: otherwise gridDim.x is re-read from the dispatch packet -- a scalar load and its
   // s_waitcnt lgkmcnt(0) -- in tile_of() of every iteration)
   asm volatile("" : "+s"(sl_n_));
-#endif
   const int sl_n = sl_n_, sl_y = (int)blockIdx.x;
   // LIST: the block's steps = the entries of its list (tile | waves that cannot rule the tile out << 24), in scan order;
   // read with scalar loads (constant address space), two steps ahead of their use
@@ -480,20 +463,20 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
     }
   }
   float wmax = INFINITY;  // max threshold over this wave's 64 queries (wave-uniform)
-  if (a.thr_init) {  // seeded thresholds also seed the pruning bound (and let the timing ablations prune realistically)
+  if (a.thr_init) {  // seeded thresholds also seed the pruning bound
     float w = fmaxf(thr_start(0), thr_start(1));
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) w = fmaxf(w, __shfl_xor(w, off, 64));
     wmax = w;
   }
-  unsigned st_go = 0;  // (EE, ABL == 2: blocks of 32 references that went on past K block 0)
-  unsigned st_slow = 0, st_app = 0, st_sq = 0;  // profiling (ABL == 2 only): slow-path entries, appends (per lane), compactions
+  unsigned st_go = 0;  // (EE: blocks of 32 references that went on past K block 0)
+  unsigned st_slow = 0, st_app = 0, st_sq = 0;  // STATS only: slow-path entries, appends (per lane), compactions
   // ... and where a wave's cycles go (s_memtime stamps at points where the LDS / scalar counter is drained anyway): MFMA segments
   // of a live step, slow path, control tail up to the tile wait, the tile wait, the tile barrier; steps sat out
   unsigned tm_seg = 0, tm_sel = 0, tm_tail = 0, tm_dma = 0, tm_bar = 0, tm_idle = 0, tm_mark = 0;
-  auto tm_now = [&]() __attribute__((always_inline)) { return ABL == 2 ? (unsigned)__builtin_readcyclecounter() : 0u; };
+  auto tm_now = [&]() __attribute__((always_inline)) { return STATS ? (unsigned)__builtin_readcyclecounter() : 0u; };
   auto tm_lap = [&](unsigned& acc) __attribute__((always_inline)) {
-    if (ABL == 2) {
+    if (STATS) {
       const unsigned n = tm_now();
       acc += n - tm_mark;
       tm_mark = n;
@@ -722,9 +705,6 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
   };
   auto refresh_wmax = [&]() __attribute__((always_inline)) {
     if (my_lb == nullptr) return;  // only the pruning test reads it
-#ifdef K16_NO_WMAX_REFRESH
-    return;  // (experiment: the live sets stay what the start thresholds make them)
-#endif
     float w = fmaxf(thrp[0] + wave_qn[jq], thrp[1] + wave_qn[32 + jq]);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) w = fmaxf(w, __shfl_xor(w, off, 64));
@@ -736,7 +716,7 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
   // is opened (padding references have |r|^2 = +inf and never pass, so no index test is needed).
   auto select = [&](const f32x16& c0, const f32x16& c1, float m0, float m1, int ref_base) __attribute__((always_inline)) {
     unsigned long long need = 0;  // rows to compact: bit 32 g + j
-    if (ABL == 2) ++st_slow;
+    if (STATS) ++st_slow;
 #pragma unroll
     for (int g = 0; g < 2; ++g) {
       const f32x16 acc = g ? c1 : c0;
@@ -748,13 +728,9 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
         const float v = acc[r];
         if (v < thrp[g]) {
           const unsigned off4 = rowoff4 + 4u * (unsigned)(g ? cnt[1]++ : cnt[0]++);
-          if (ABL == 2) ++st_app;
-          if (ABL == 5) {  // (timing-only ablation: the append without its stores)
-            asm volatile("" ::"v"(off4));
-          } else {
-            *reinterpret_cast<float*>(reinterpret_cast<char*>(wave_d2) + off4) = v;  // raw: |q|^2 is added when the row is ranked
-            *reinterpret_cast<int*>(reinterpret_cast<char*>(wave_idx) + off4) = ref_base + (r & 3) + 8 * (r >> 2);
-          }
+          if (STATS) ++st_app;
+          *reinterpret_cast<float*>(reinterpret_cast<char*>(wave_d2) + off4) = v;  // raw: |q|^2 is added when the row is ranked
+          *reinterpret_cast<int*>(reinterpret_cast<char*>(wave_idx) + off4) = ref_base + (r & 3) + 8 * (r >> 2);
         }
       };
 #pragma unroll
@@ -776,7 +752,7 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
         const int j = __ffsll((long long)need) - 1;
         need &= need - 1;
         squeeze(j >> 5, j & 31);
-        if (ABL == 2) ++st_sq;
+        if (STATS) ++st_sq;
       }
       refresh_wmax();
       K16_COLD_REGION_END();
@@ -800,7 +776,7 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
     } else {
       // A_AHEAD A fragments in flight: the fragment of K block kb + A_AHEAD is requested right after the MFMAs of
       // block kb have issued (with |q|^2 out of the registers the budget of three waves per SIMD has room for four)
-      constexpr int A_AHEAD = K16_A_AHEAD;  // A fragments in flight
+      constexpr int A_AHEAD = 4;  // A fragments in flight (measured 2 -> 4: -2 %)
       __builtin_amdgcn_sched_group_barrier(0x100, KB < A_AHEAD ? KB : A_AHEAD, 0);
       __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
 #pragma unroll
@@ -821,29 +797,19 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
   auto segment = [&](const _Float16* tile, int sub, f32x16& n0, f32x16& n1, const f32x16& c0, const f32x16& c1, int ref_base, bool issue,
                      bool fresh) __attribute__((always_inline)) {
     if (issue) mfma_block(tile, sub, n0, n1);
-    if (ABL == 3 || ABL == 4 || ABL == 8 || ABL == 9 || ABL == 10) {  // profiling ablation: MFMAs only, accumulators kept live
-      asm volatile("" ::"v"(c0[0]), "v"(c0[15]), "v"(c1[0]), "v"(c1[15]));
-      return;
-    }
     float m0, m1;
     vote(c0, c1, m0, m1);
-#ifndef K16_NO_VOTE_PIN
     // The minima are needed only when the block is `fresh`, and where that is not a constant (the first segment of a step)
     // the compiler sinks the whole vote behind the branch on it -- out of the basic block of the MFMAs, i.e. the 8 MFMAs
     // issue back to back and the ~20 VALU instructions of the vote afterwards, instead of two per MFMA slot.  An asm use
     // pins them to this block.
     if (issue) asm volatile("" : "+v"(m0), "+v"(m1));
-#endif
     const bool hit = m0 < thrp[0] || m1 < thrp[1];
     if (issue) pipeline_order();
-    if (ABL == 1) {  // profiling ablation: distances + minimum, selection removed
-      asm volatile("" ::"v"(m0), "v"(m1));
-      return;
-    }
     if (fresh && __any(hit)) {
       unsigned t0s = tm_now();
       select(c0, c1, m0, m1, ref_base);
-      if (ABL == 2) {
+      if (STATS) {
         const unsigned d = tm_now() - t0s;
         tm_sel += d;
         tm_mark += d;  // (not counted as segment time)
@@ -914,7 +880,7 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
         if (__any(m0 < thrp[0] || m1 < thrp[1])) {
           const unsigned t0s = tm_now();
           select(accA0, accA1, m0, m1, t * K16_TS + 32 * sub + 4 * h);
-          if (ABL == 2) {
+          if (STATS) {
             const unsigned dsel = tm_now() - t0s;
             tm_sel += dsel;
             tm_mark += dsel;  // (not counted as segment time)
@@ -946,8 +912,8 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
   }
   // tiles of steps 0 and s_next requested; the first one has to be there
   if constexpr (!PAIR) {
-    if (s_next < n_scan && ABL != 9) {
-      K16_LOAD(__builtin_amdgcn_readfirstlane(ABL == 8 ? (t_next & 63) : t_next), (unsigned)TILE_LDS_BYTES);
+    if (s_next < n_scan) {
+      K16_LOAD(__builtin_amdgcn_readfirstlane(t_next), (unsigned)TILE_LDS_BYTES);
       K16_STAGED_BUT_LAST();
     } else {
       K16_STAGED();
@@ -962,29 +928,13 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
     const bool tm_live = live_cur;
     unsigned e_far = 0u;  // LIST: the entry two steps past s_next, requested a whole iteration before it is needed
     if constexpr (LIST) e_far = list_entry(s_next + 2);
-#ifdef K16_LIST_LOAD_TOP
-    // LIST: the step after next is known here, so its tile is requested before the MFMA segments (the buffer it goes to was
-    // read by the previous iteration and every wave has passed the barrier behind that)
-    int s_nn_top = 0, t_nn_top = 0;
-    if constexpr (LIST) {
-      s_nn_top = min(s_next + 1, n_scan);
-      t_nn_top = s_nn_top < n_scan ? (int)(e_pref & 0xFFFFFFu) : t_next;
-      if (s_nn_top < n_scan) K16_LOAD(__builtin_amdgcn_readfirstlane(t_nn_top), wr_b);
-    }
-#endif
     if (EE && live_cur) {
       ee_tile(tile_r, t);
     } else if (live_cur) {
-#ifdef K16_SETPRIO
-      __builtin_amdgcn_s_setprio(K16_SETPRIO);
-#endif
       // sub-tile 0 on the pipe while sub-tile 1 of the previous tile is voted on
       segment(tile_r, 0, accA0, accA1, accB0, accB1, refB, true, pend);
       // sub-tile 1 on the pipe while sub-tile 0 is voted on
       segment(tile_r, 1, accB0, accB1, accA0, accA1, t * K16_TS + 4 * h, true, true);
-#ifdef K16_SETPRIO
-      __builtin_amdgcn_s_setprio(0);
-#endif
       refB = t * K16_TS + 32 + 4 * h;
       pend = true;
       ++n_done;
@@ -1016,7 +966,7 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
           const int j = __ffsll((long long)todo) - 1;
           todo &= todo - 1;
           squeeze(j >> 5, j & 31);
-          if (ABL == 2) ++st_sq;
+          if (STATS) ++st_sq;
         }
         refresh_wmax();
         K16_COLD_REGION_END();
@@ -1038,26 +988,21 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
 
     // request the tile of the step after next (into the buffer the previous iteration read: every wave has passed
     // the barrier behind it), then wait for the tile of the next step, requested one iteration ago
-    if (ABL != 9) {  // (8 / 9 = timing-only ablations: tiles from a 64-tile hot set / no tile loads)
-      if (s_nn < n_scan) {
-#ifdef K16_LIST_LOAD_TOP
-        if constexpr (!LIST)
-#endif
-        K16_LOAD(__builtin_amdgcn_readfirstlane(ABL == 8 ? (t_nn & 63) : t_nn), wr_b);
-        tm_lap(tm_tail);
-        K16_STAGED_BUT_LAST();
-      } else {
-        tm_lap(tm_tail);
-        K16_STAGED();
-      }
-      tm_lap(tm_dma);
+    if (s_nn < n_scan) {
+      K16_LOAD(__builtin_amdgcn_readfirstlane(t_nn), wr_b);
+      tm_lap(tm_tail);
+      K16_STAGED_BUT_LAST();
+    } else {
+      tm_lap(tm_tail);
+      K16_STAGED();
     }
+    tm_lap(tm_dma);
     if (my_lb) {
       my_live = __ballot(win_lb <= wmax + prune_margin);
       if (lane == 0) lds_wlive[par ^ 1][wave] = my_live;
     }
     tm_lap(tm_tail);
-    if (ABL != 10 && (ABL != 4 || (s_cur & 1))) K16_TILE_BARRIER();  // (4 / 10 = timing-only ablations: MFMAs only, a barrier every other tile / none)
+    K16_TILE_BARRIER();
     tm_lap(tm_bar);
     s_cur = s_next;
     t_cur = t_next;
@@ -1108,7 +1053,7 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
           const int j = __ffsll((long long)todo) - 1;
           todo &= todo - 1;
           squeeze(j >> 5, j & 31);
-          if (ABL == 2) ++st_sq;
+          if (STATS) ++st_sq;
         }
       }
       tm_lap(tm_tail);
@@ -1133,8 +1078,8 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, ABL, NPROD) + ((EE && K16_EE_PA
     }
   }
 
-  unsigned long long* stats = ABL == 2 ? K16_COLD(stats) : nullptr;
-  if (ABL == 2 && stats) {  // profiling counters requested (MELD_KNN16_STATS): wave-blocks, slow-path entries, appends, compactions
+  unsigned long long* stats = STATS ? K16_COLD(stats) : nullptr;
+  if (STATS && stats) {  // counters requested (MELD_KNN16_STATS): wave-blocks, slow-path entries, appends, compactions
     unsigned a = st_app;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) a += __shfl_xor(a, off, 64);
@@ -1211,8 +1156,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
                                                                    const float* __restrict__ norm2_max, const float* __restrict__ thr_init,
                                                                    unsigned* step_list, const int* __restrict__ step_cnt, long long list_stride,
                                                                    int* __restrict__ cnt_out, unsigned long long* __restrict__ tested,
-                                                                   const int* __restrict__ block_order, int KB, int ee_hi, int abl) {
-  // (abl: timing-only ablations of -DK16_PROFILING builds, MELD_KNN_FILTER_ABL: 1 = no staging behind the first step, 2 = no tests)
+                                                                   const int* __restrict__ block_order, int KB, int ee_hi) {
   static_assert(TPS >= 2 && TPS <= 32 && (TPS & 1) == 0, "tiles per step");
   __shared__ __attribute__((aligned(16))) _Float16 ring[2][TPS][2 * K16_TS * 8];  // K block 0, hi planes: [k-half][ref][8 halves]
   __shared__ unsigned wmask[2][4];
@@ -1301,13 +1245,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
   for (int s = 0; s < n_steps; ++s) {
     const int buf = s & 1;
     const unsigned ev_nn = load_entries(s + 2);
-    if (s + 1 < n_steps && !(abl & 1)) stage(ev_nxt, buf ^ 1);
+    if (s + 1 < n_steps) stage(ev_nxt, buf ^ 1);
     if (wave == 0 && s > 0) emit(ev_prev, buf ^ 1);
     unsigned mybits = 0u;
 #pragma unroll
     for (int j = 0; j < TPS; ++j) {
       const unsigned e = (unsigned)__builtin_amdgcn_readlane((int)ev_cur, j);
-      if (((e >> (24 + wave)) & 1u) && !(abl & 2)) {
+      if ((e >> (24 + wave)) & 1u) {
         const f16x8* a8 = reinterpret_cast<const f16x8*>(&ring[buf][j][0]) + jq;
         const f16x8 aA = a8[h * K16_TS], aB = a8[h * K16_TS + 32];
         // (four independent accumulators; one pair after the other -- 55 instead of 70 registers, up to eight waves per SIMD --
@@ -1552,10 +1496,7 @@ __global__ __launch_bounds__(256) void tile_spheres_kernel(const double* __restr
       return m;
     };
     float best = INFINITY;
-#ifndef K16_MEB_STEPS
-#define K16_MEB_STEPS 24
-#endif
-    constexpr int MEB_STEPS = K16_MEB_STEPS;
+    constexpr int MEB_STEPS = 24;
     for (int it = 1; it <= MEB_STEPS + 1; ++it) {
       int who;
       const float r2 = far2(&who);
@@ -2125,12 +2066,8 @@ __global__ __launch_bounds__(64 * SEED_WAVES) void knn16_seed_mfma_kernel(const 
 using namespace meld;
 
 // SPLIT operand layout (k16_slot): wherever it fits.  A function of d alone: no process-wide switch (the boundary's contract is
-// "no global state"); the plain layout for A-B measurements is a compile-time choice of a development build (-DK16_PLAIN_LAYOUT).
-#ifdef K16_PLAIN_LAYOUT
-static int k16_dA(int, int) { return 0; }
-#else
-static int k16_dA(int d, int KB) { return k16_split_dims_of(d, KB, 1); }
-#endif
+// "no global state").
+static int k16_dA(int d, int KB) { return (d > K16_SPLIT_DA && d + 6 <= 16 * KB) ? K16_SPLIT_DA : 0; }
 extern "C" int meld_knn16_kblocks(int d);
 // coordinates K block 0 holds under the SPLIT layout (the list-driven first pass tests its accumulators behind that block: the
 // caller does well to hand the cells over in a frame whose leading coordinates carry the distances); 0: plain layout
@@ -2447,17 +2384,15 @@ static int k16_bounds_impl(const double* X, int64_t N, int d, const double* mean
       K16_BOUNDS_LAUNCH(KBV, false, (KBV <= 4 ? K16_BOUNDS_THREADS : K16_BOUNDS_THREADS / 2));                            \
     break;
   switch (KB) {
-    K16_BOUNDS_CASE(4)
-#ifndef K16_DEV_KB4
     K16_BOUNDS_CASE(1)
     K16_BOUNDS_CASE(2)
     K16_BOUNDS_CASE(3)
+    K16_BOUNDS_CASE(4)
     K16_BOUNDS_CASE(5)
     K16_BOUNDS_CASE(6)
     K16_BOUNDS_CASE(7)
     K16_BOUNDS_CASE(8)
     K16_BOUNDS_CASE(9)
-#endif
     default:
       set_err("meld_knn16_bounds: no kernel for %d K blocks", KB);
       return MELD_ERR_UNSUPPORTED;
@@ -2701,7 +2636,7 @@ static int k16_step_lists_direct_impl(const double* X, int64_t N, int d, const d
   const float ec = (float)meld_knn16_error_coef(1, d);
   // lead_only (the caller's word that the leading coordinates carry the distances, SPLIT layout only): bounds from K block 0 alone
   const int dA = k16_dA(d, KB);
-  const bool lead = lead_only != 0 && dA > 0 && KB >= 2 && !(meld_dev_getenv("MELD_KNN16_LEAD_BOUNDS") && atoi(meld_dev_getenv("MELD_KNN16_LEAD_BOUNDS")) == 0);
+  const bool lead = lead_only != 0 && dA > 0 && KB >= 2;
 #define K16_BITS_LAUNCH(KBV, BTV)                                                                                          \
   if (lead)                                                                                                                \
     hipLaunchKernelGGL((knn16_tile_bounds_kernel<KBV, true, BTV, true, (KBV >= 2 ? 1 : KBV)>), dim3(gx, gy), dim3(BTV), 0, st, c16, cn, cr, \
@@ -2718,17 +2653,15 @@ static int k16_step_lists_direct_impl(const double* X, int64_t N, int d, const d
     K16_BITS_LAUNCH(KBV, (KBV <= 4 ? K16_BOUNDS_THREADS : K16_BOUNDS_THREADS / 2)); \
     break;
   switch (KB) {
-    K16_BITS_CASE(4)
-#ifndef K16_DEV_KB4
     K16_BITS_CASE(1)
     K16_BITS_CASE(2)
     K16_BITS_CASE(3)
+    K16_BITS_CASE(4)
     K16_BITS_CASE(5)
     K16_BITS_CASE(6)
     K16_BITS_CASE(7)
     K16_BITS_CASE(8)
     K16_BITS_CASE(9)
-#endif
     default:
       set_err("meld_knn16_step_lists_direct: no kernel for %d K blocks", KB);
       return MELD_ERR_UNSUPPORTED;
@@ -2801,17 +2734,15 @@ extern "C" int meld_knn16_seed_thresholds_mfma(const void* Q16, const float* Qn,
       K16_SEEDM_LAUNCH(KBV, 64);     \
     break;
   switch (KB) {
-    K16_SEEDM_CASE(4)
-#ifndef K16_DEV_KB4
     K16_SEEDM_CASE(1)
     K16_SEEDM_CASE(2)
     K16_SEEDM_CASE(3)
+    K16_SEEDM_CASE(4)
     K16_SEEDM_CASE(5)
     K16_SEEDM_CASE(6)
     K16_SEEDM_CASE(7)
     K16_SEEDM_CASE(8)
     K16_SEEDM_CASE(9)
-#endif
     default:
       set_err("meld_knn16_seed_thresholds_mfma: no kernel for %d K blocks", KB);
       return MELD_ERR_UNSUPPORTED;
@@ -2820,6 +2751,24 @@ extern "C" int meld_knn16_seed_thresholds_mfma(const void* Q16, const float* Qn,
 #undef K16_SEEDM_LAUNCH
   MELD_LAUNCH_CHECK("knn16_seed_mfma_kernel");
   return MELD_OK;
+}
+
+// One search launch: the pruning-table kernel (nprod 1 or 3), the list-driven one, or the list-driven one with the partial test.
+template <int KB, int STATS>
+static void k16_launch_topk(dim3 grid, hipStream_t st, const K16Args& ka, bool listed, bool ee, int nprod) {
+  if (listed) {
+    if constexpr (KB >= 2 && KB <= 7) {
+      if (ee) {
+        hipLaunchKernelGGL((knn16_topk_kernel<KB, STATS, 1, true, true>), grid, dim3(K16_THREADS), 0, st, ka);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((knn16_topk_kernel<KB, STATS, 1, true>), grid, dim3(K16_THREADS), 0, st, ka);
+  } else if (nprod == 1) {
+    hipLaunchKernelGGL((knn16_topk_kernel<KB, STATS, 1>), grid, dim3(K16_THREADS), 0, st, ka);
+  } else {
+    hipLaunchKernelGGL((knn16_topk_kernel<KB, STATS, 3>), grid, dim3(K16_THREADS), 0, st, ka);
+  }
 }
 
 static int k16_topk_impl(const void* Q16, const float* Qn, const void* Rt16, const float* scale_info,
@@ -2857,24 +2806,10 @@ static int k16_topk_impl(const void* Q16, const float* Qn, const void* Rt16, con
   MELD_CHECK_ARG(grid.y <= 65535u, "meld_knn16_topk: more than 65535 query blocks in one launch");
   MELD_CHECK_ARG(n_slices <= ceil_div(n_ref, K16_TS), "meld_knn16_topk: more slices than reference tiles");
   const int tile_origin = (int)((q_begin / K16_TS) % n_tiles);  // the scan starts at the queries' own position
-  // profiling hooks (never set in production): MELD_KNN16_ABLATION=1 distances without selection,
-  // =3 MFMAs only; MELD_KNN16_PADLDS=<bytes> extra dynamic LDS to lower the workgroups per CU
-  const char* abl_env = meld_dev_getenv("MELD_KNN16_ABLATION");
-  const int abl = abl_env ? atoi(abl_env) : 0;
-  const char* pad_env = meld_dev_getenv("MELD_KNN16_PADLDS");
-  const size_t pad_lds = pad_env ? (size_t)atoi(pad_env) : 0;
   const _Float16* q = reinterpret_cast<const _Float16*>(Q16);
   const _Float16* r = reinterpret_cast<const _Float16*>(Rt16);
   unsigned long long* stats = nullptr;
-  // batched compaction: every 64 tiles, rows with > ksel + 64 entries (with the seeded thresholds the rows fill slowly:
-  // 32 / 32, the setting before the seeds, costs 0.9 ms more at 1M cells; none at all 0.4 ms more)
-  int batch_every = 64, batch_slack = 64;
-  if (const char* e = meld_dev_getenv("MELD_KNN16_BATCH_EVERY")) {  // profiling hooks (a power of two, or 0 = off)
-    batch_every = atoi(e);
-    MELD_CHECK_ARG(batch_every >= 0 && (batch_every & (batch_every - 1)) == 0, "MELD_KNN16_BATCH_EVERY must be a power of two");
-  }
-  if (const char* e = meld_dev_getenv("MELD_KNN16_BATCH_SLACK")) batch_slack = std::max(0, atoi(e));
-  if (meld_dev_getenv("MELD_KNN16_STATS")) {  // profiling hook: selection counters, printed after the launch
+  if (meld_dev_getenv("MELD_KNN16_STATS")) {  // diagnostic: selection counters, printed after the launch
     static unsigned long long* counters[64] = {nullptr};  // (a racing first call leaks 256 B at worst)
     int dev = 0;
     MELD_HIP_CALL(hipGetDevice(&dev));
@@ -2896,8 +2831,10 @@ static int k16_topk_impl(const void* Q16, const float* Qn, const void* Rt16, con
   ka.norm2_max = norm2_max;
   ka.err_coef = (float)meld_knn16_error_coef(nprod, d);
   ka.tile_origin = tile_origin;
-  ka.batch_every = batch_every;
-  ka.batch_slack = batch_slack;
+  // batched compaction: every 64 tiles, rows with > ksel + 64 entries (with the seeded thresholds the rows fill slowly:
+  // 32 / 32, the setting before the seeds, costs 0.9 ms more at 1M cells; none at all 0.4 ms more)
+  ka.batch_every = 64;
+  ka.batch_slack = 64;
   ka.two_sided = 1;
   ka.stats = stats;
   ka.thr_init = thr_init;
@@ -2916,108 +2853,36 @@ static int k16_topk_impl(const void* Q16, const float* Qn, const void* Rt16, con
   ka.list_stride = (long long)list_stride;
   // the list-driven first pass tests its blocks behind K block 0 where the operands carry the SPLIT layout and the caller asks
   // for it (`partial_test`: it knows whether the leading coordinates carry the distances -- where they do not, the test drops
-  // nothing and costs 15 %); MELD_KNN16_EE=0 / 1 overrides the caller, for A-B measurements
+  // nothing and costs 15 %); seven K blocks (d = 100, the reference's default n_pca) is the largest partial-test kernel
   const int dA = k16_dA(d, KB);
-  const char* ee_env = meld_dev_getenv("MELD_KNN16_EE");
-  const bool ee = step_list != nullptr && dA > 0 && KB >= 2 && KB <= 7 && (ee_env ? atoi(ee_env) != 0 : partial_test != 0);
+  const bool ee = step_list != nullptr && dA > 0 && KB >= 2 && KB <= 7 && partial_test != 0;
   ka.ee_hi = 16 + d - dA;
-  ka.count_go = two_counters;  // (a caller of meld_knn16_topk_listed passes ONE counter, whatever MELD_KNN16_EE forces)
+  ka.count_go = two_counters;  // (a caller of meld_knn16_topk_listed passes ONE counter)
   ka.planes_used = ((dA > 0 ? 16 + (d - dA) + 3 : d + 3) + 7) / 8;  // (the padding plane behind the used K slots is never copied)
-#ifndef K16_PROFILING
-  MELD_CHECK_ARG(abl == 0, "MELD_KNN16_ABLATION needs a library built with -DK16_PROFILING");
-#endif
-#ifdef K16_PROFILING  // the timing-only ablations of the list-driven kernel (8: tiles from a 64-tile hot set, 9: no tile loads, 1: no selection)
-#define K16_DEV_LIST_ABL(KBV)                                                                                       \
-  if (abl == 9) hipLaunchKernelGGL((knn16_topk_kernel<KBV, 9, 1, true>), grid, dim3(K16_THREADS), pad_lds, S(stream), ka); \
-  else if (abl == 8) hipLaunchKernelGGL((knn16_topk_kernel<KBV, 8, 1, true>), grid, dim3(K16_THREADS), pad_lds, S(stream), ka); \
-  else if (abl == 1) hipLaunchKernelGGL((knn16_topk_kernel<KBV, 1, 1, true>), grid, dim3(K16_THREADS), pad_lds, S(stream), ka); \
-  else
-#else
-#define K16_DEV_LIST_ABL(KBV)
-#endif
-#define K16_LAUNCH2(KBV, ABLV, NP) \
-  hipLaunchKernelGGL((knn16_topk_kernel<KBV, ABLV, NP>), grid, dim3(K16_THREADS), pad_lds, S(stream), ka)
-#define K16_LAUNCH(KBV, ABLV)        \
-  do {                               \
-    if (step_list != nullptr) {      \
-      K16_DEV_LIST_ABL(KBV)          \
-      if (ee && KBV >= 2 && KBV <= 7) { /* (seven K blocks: d = 100, the reference's default n_pca; eight and nine are not instantiated) */ \
-        if (stats != nullptr)        \
-          hipLaunchKernelGGL((knn16_topk_kernel<((KBV >= 2 && KBV <= 7) ? KBV : 2), 2, 1, true, true>), grid, dim3(K16_THREADS), pad_lds, S(stream), ka); \
-        else                         \
-          hipLaunchKernelGGL((knn16_topk_kernel<((KBV >= 2 && KBV <= 7) ? KBV : 2), 0, 1, true, true>), grid, dim3(K16_THREADS), pad_lds, S(stream), ka); \
-      } else if (stats != nullptr)   \
-        hipLaunchKernelGGL((knn16_topk_kernel<KBV, 2, 1, true>), grid, dim3(K16_THREADS), pad_lds, S(stream), ka); \
-      else                           \
-        hipLaunchKernelGGL((knn16_topk_kernel<KBV, 0, 1, true>), grid, dim3(K16_THREADS), pad_lds, S(stream), ka); \
-    } else if (nprod == 1)           \
-      K16_LAUNCH2(KBV, ABLV, 1);     \
-    else                             \
-      K16_LAUNCH2(KBV, ABLV, 3);     \
-  } while (0)
-#ifndef K16_PROFILING  // product builds: the search and its counters (MELD_KNN16_STATS); the timing-only ablations of tools/knn_ablate.py are
-                       // compiled with -DK16_PROFILING (tools/build_variant.sh prof knn16.hip -DK16_PROFILING [-DK16_DEV_KB4 = d <= 61 only])
-#define K16_CASE(KBV)                  \
-  case KBV:                            \
-    if (stats != nullptr)              \
-      K16_LAUNCH(KBV, 2);              \
-    else                               \
-      K16_LAUNCH(KBV, 0);              \
+#define K16_CASE(KBV)                                                                                                      \
+  case KBV:                                                                                                                \
+    (stats ? k16_launch_topk<KBV, 1> : k16_launch_topk<KBV, 0>)(grid, S(stream), ka, step_list != nullptr, ee, nprod); \
     break;
-#else
-#define K16_CASE(KBV)                  \
-  case KBV:                            \
-    if (abl == 1)                      \
-      K16_LAUNCH(KBV, 1);              \
-    else if (abl == 3)                 \
-      K16_LAUNCH(KBV, 3);              \
-    else if (abl == 4 && KBV == 4)     \
-      K16_LAUNCH(4, 4);                \
-    else if (abl == 5 && KBV == 4)     \
-      K16_LAUNCH(4, 5);                \
-    else if (abl == 7 && KBV == 4)     \
-      K16_LAUNCH(4, 7);                \
-    else if (abl == 10 && KBV == 4)    \
-      K16_LAUNCH(4, 10);               \
-    else if (abl == 8 && KBV == 4)     \
-      K16_LAUNCH(4, 8);                \
-    else if (abl == 9 && KBV == 4)     \
-      K16_LAUNCH(4, 9);                \
-    else if (stats != nullptr)         \
-      K16_LAUNCH(KBV, 2);              \
-    else if (abl == 6 && KBV <= 4)     \
-      K16_LAUNCH((KBV <= 4 ? KBV : 1), 6); \
-    else                               \
-      K16_LAUNCH(KBV, 0);              \
-    break;
-#endif
   switch (KB) {
-    K16_CASE(4)
-#ifndef K16_DEV_KB4
     K16_CASE(1)
     K16_CASE(2)
     K16_CASE(3)
+    K16_CASE(4)
     K16_CASE(5)
     K16_CASE(6)
     K16_CASE(7)
     K16_CASE(8)
     K16_CASE(9)
-#endif
     default:
       set_err("meld_knn16_topk: KB=%d is not an instantiated size", KB);
       return MELD_ERR_UNSUPPORTED;
   }
 #undef K16_CASE
-#undef K16_LAUNCH
-#undef K16_LAUNCH2
   MELD_LAUNCH_CHECK("knn16_topk_kernel");
-  if (abl == 0 || abl == 2 || abl == 5 || abl == 6) {  // (the timing-only ablations leave no rows to sort)
-    const int64_t n_rows = (int64_t)grid.x * K16_BQ * grid.y;
-    const dim3 fgrid((unsigned)ceil_div(n_rows, 4));
-    hipLaunchKernelGGL(knn16_finish_rows_kernel, fgrid, dim3(256), 0, S(stream), cand_d2, cand_idx, cand_cnt, Qn, scale_info, n_rows,
-                       (int64_t)grid.y * K16_BQ, cap, ksel);
-    MELD_LAUNCH_CHECK("knn16_finish_rows_kernel");
-  }
+  const int64_t n_rows = (int64_t)grid.x * K16_BQ * grid.y;
+  hipLaunchKernelGGL(knn16_finish_rows_kernel, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, S(stream), cand_d2, cand_idx, cand_cnt, Qn,
+                     scale_info, n_rows, (int64_t)grid.y * K16_BQ, cap, ksel);
+  MELD_LAUNCH_CHECK("knn16_finish_rows_kernel");
   if (stats) {
     unsigned long long st[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     MELD_HIP_CALL(hipStreamSynchronize(S(stream)));
@@ -3095,13 +2960,9 @@ extern "C" int meld_knn16_partial_filter(const void* Q16, const float* Qn, const
   const int dA = k16_dA(d, KB);
   MELD_CHECK_ARG(dA > 0 && KB >= 2, "meld_knn16_partial_filter: d = %d has no split operand layout", d);
   const unsigned n_blocks = (unsigned)ceil_div(q_count, K16_BQ);
-  int abl = 0;
-#ifdef K16_PROFILING
-  if (const char* e = meld_dev_getenv("MELD_KNN_FILTER_ABL")) abl = atoi(e);
-#endif
   hipLaunchKernelGGL((knn16_partial_filter_kernel<8, 4>), dim3(n_blocks), dim3(256), 0, S(stream), reinterpret_cast<const _Float16*>(Q16), Qn,
                      reinterpret_cast<const _Float16*>(Rt16), scale_info, norm2_max, thr_init, step_list, step_cnt, (long long)list_stride, cnt_out,
-                     reinterpret_cast<unsigned long long*>(tested), block_order, KB, 16 + d - dA, abl);
+                     reinterpret_cast<unsigned long long*>(tested), block_order, KB, 16 + d - dA);
   MELD_LAUNCH_CHECK("knn16_partial_filter_kernel");
   return MELD_OK;
 }
@@ -3123,17 +2984,15 @@ extern "C" int meld_knn16_resident_blocks(int d, int nprod) {
     }                                                                                                             \
     break;
   switch (KB) {
-    K16_OCC(4)
-#ifndef K16_DEV_KB4
     K16_OCC(1)
     K16_OCC(2)
     K16_OCC(3)
+    K16_OCC(4)
     K16_OCC(5)
     K16_OCC(6)
     K16_OCC(7)
     K16_OCC(8)
     K16_OCC(9)
-#endif
     default:
       return MELD_ERR_UNSUPPORTED;
   }

@@ -814,7 +814,7 @@ class HipOps:
             step_cnt = torch.empty(n_blocks, dtype=torch.int32, device=dev)
             scratch = torch.empty(lib.meld_knn16_list_scratch_bytes(N), dtype=torch.uint8, device=dev)
             check(lib.meld_knn16_step_lists_direct_lead(ptr(X_s), N, d, ptr(mean_s), ptr(o.scale_info), ptr(nmax), ptr(o.Rt), ptr(seeds), ptr(o.Qn), plan.nprod,
-                                                        ptr(tmpb), ptr(scratch), ptr(step_list), n_tiles, ptr(step_cnt), int(plan.partial_in_search), st),
+                                                        ptr(tmpb), ptr(scratch), ptr(step_list), n_tiles, ptr(step_cnt), int(plan.lead_bounds), st),
                   "meld_knn16_step_lists_direct")
             del scratch
         else:

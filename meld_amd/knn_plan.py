@@ -13,6 +13,7 @@ from __future__ import annotations
 import ctypes
 import dataclasses
 from dataclasses import dataclass
+from typing import Optional
 
 from ._lib import check
 from ._options import opt
@@ -70,10 +71,18 @@ class KnnPlan:
     two_pass: bool           # the partial test as a filter pass of its own (meld_knn16_partial_filter)
     partial_in_search: bool  # the K-block-0 partial test inside the search
     stage2: bool             # uncertified rows searched again with the full hi/lo split
+    # the direct step lists take their bounds from K block 0 alone (None: as the route implies, i.e. direct lists in the frame)
+    lead_bounds: Optional[bool] = None
+    partial_forced: bool = False  # partial_in_search set by MELD_KNN16_EE, not by the frame: without_frame() keeps it
+
+    def __post_init__(self):
+        if self.lead_bounds is None:
+            object.__setattr__(self, "lead_bounds", self.lists == "direct" and self.frame)
 
     def without_frame(self):
         """The same route with the cells as given (the frame's leading coordinates carry less than half the variance)."""
-        return dataclasses.replace(self, frame=False, two_pass=False, partial_in_search=False)
+        return dataclasses.replace(self, frame=False, two_pass=False, lead_bounds=False,
+                                   partial_in_search=self.partial_in_search and self.partial_forced)
 
 
 def search_nprod(nprod, d):
@@ -133,10 +142,17 @@ def plan_knn_search(lib, N, d, q_begin, q_count, knn, ksel, *, options, cross=Fa
         # out (more slices cost more in merging than they balance).
         if radius_cut and resident > 0 and n_blocks < 2 * resident:
             main_slices = int(max(1, min(4, lib.meld_knn16_max_slices(ksel), -(-2 * resident // n_blocks), n_tiles // 64)))
-    # The partial test of the principal frame as a pass of its own: every listed (wave, tile) pair is tested on K block 0 and the
-    # lists are thinned in place before the search.  Sliced launches (few query blocks) keep the one-kernel form: a workgroup of
-    # the filter walks its block's whole list.  MELD_KNN_TWO_PHASE=0: always the one-kernel form, =2: also when sliced.
+    # The partial test (K block 0 first, the other blocks only where it passes) pays in the principal frame, whose leading
+    # coordinates carry the distances.  MELD_KNN16_EE=0 / 1 forces it off / on inside the search, frame or not, with no filter pass.
+    ee = opt("MELD_KNN16_EE")
+    partial = frame if ee is None else ee != "0"
+    # ... as a pass of its own: every listed (wave, tile) pair is tested on K block 0 and the lists are thinned in place before the
+    # search.  Sliced launches (few query blocks) keep the one-kernel form: a workgroup of the filter walks its block's whole list.
+    # MELD_KNN_TWO_PHASE=0: always the one-kernel form, =2: also when sliced.
     two = opt("MELD_KNN_TWO_PHASE", "1")
-    two_pass = lists != "none" and frame and (main_slices == 1 or two == "2") and two != "0" and opt("MELD_KNN16_EE") is None
+    two_pass = lists != "none" and frame and (main_slices == 1 or two == "2") and two != "0" and ee is None
+    # the direct lists in the frame take their bounds from K block 0 alone (lower bounds all the same, for a quarter of the tile
+    # stream); MELD_KNN16_LEAD_BOUNDS=0: from all K blocks
+    lead_bounds = lists == "direct" and frame and opt("MELD_KNN16_LEAD_BOUNDS", "1") != "0"
     return KnnPlan(search, nprod, frame, radius_cut, prune, seed, 0 if seed == "bandwidth" else knn, bounds, seeded_bounds, lists,
-                   block_order, main_slices, two_pass, frame, nprod == 1)
+                   block_order, main_slices, two_pass, partial, nprod == 1, lead_bounds, ee is not None)

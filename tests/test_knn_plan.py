@@ -113,3 +113,27 @@ def test_options_switch_single_decisions(lib, monkeypatch):
     assert plan(lib, 200_000, 50) == route(bounds="bounds", lists="table", main_slices=2)
     monkeypatch.setenv("MELD_KNN_TWO_PHASE", "0")
     assert not plan(lib, 1_000_000, 50).two_pass
+
+
+def test_partial_test_and_lead_bounds_switches(lib, monkeypatch):
+    # (development switches: read under MELD_DEV=1 only, and only by the plan -- the library follows what it is handed)
+    monkeypatch.setenv("MELD_DEV", "1")
+    headline = route(frame=True, lists="direct", two_pass=True, partial_in_search=True)
+    assert headline.lead_bounds and not route(lists="direct").lead_bounds and not route(frame=True, lists="table").lead_bounds
+    monkeypatch.setenv("MELD_KNN16_EE", "0")  # the frame without the test, and no filter pass
+    p = plan(lib, 1_000_000, 50)
+    assert p == route(frame=True, lists="direct", partial_forced=True)
+    assert p.without_frame() == route(lists="direct", partial_forced=True)
+    monkeypatch.setenv("MELD_KNN16_EE", "1")  # the test in the search, frame or not, and no filter pass
+    p = plan(lib, 1_000_000, 50)
+    assert p == route(frame=True, lists="direct", partial_in_search=True, partial_forced=True)
+    assert p.without_frame() == route(lists="direct", partial_in_search=True, partial_forced=True)
+    assert plan(lib, 200_000, 50) == route(lists="direct", main_slices=2, partial_in_search=True, partial_forced=True)
+    monkeypatch.delenv("MELD_KNN16_EE")
+    assert plan(lib, 1_000_000, 50) == headline
+    monkeypatch.setenv("MELD_KNN16_LEAD_BOUNDS", "0")  # the direct lists' bounds from all K blocks
+    assert plan(lib, 1_000_000, 50) == route(frame=True, lists="direct", two_pass=True, partial_in_search=True, lead_bounds=False)
+    assert not plan(lib, 1_000_000, 50).without_frame().lead_bounds
+    monkeypatch.setenv("MELD_DEV", "0")  # (outside development mode neither switch is read)
+    monkeypatch.setenv("MELD_KNN16_EE", "0")
+    assert plan(lib, 1_000_000, 50) == headline

@@ -89,14 +89,6 @@ PY
   echo "## MELD_KNN_ROTATE=0: cells as given (no frame, no test)"; MELD_KNN_ROTATE=0 python tools/knn_only.py 1000000 3 2>&1 | grep -v amdgpu.ids | tail -1
   echo "## counters of the search kernel behind the filter (MELD_KNN16_STATS): blocks, slow path, appends, where a wave's cycles go"
   MELD_KNN16_STATS=1 python tools/knn_only.py 1000000 1 2>&1 | grep "stats" | head -3
-  # (meld_amd/libmeld_hip_prof.so: built BEFORE the call, on the build host -- `bash tools/build_variant.sh prof knn16.hip -DK16_PROFILING`;
-  # the object files it links against do not travel to the GPU box)
-  if [ -f meld_amd/libmeld_hip_prof.so ]; then
-    echo "## filter pass, timing-only ablations of the -DK16_PROFILING build (MELD_KNN_FILTER_ABL: 0 = product, 1 = no staging behind the first step, 2 = no tests, 3 = neither); knn_filter in ms"
-    for a in 0 1 2 3; do echo -n "abl $a: "; MELD_HIP_LIB=$PWD/meld_amd/libmeld_hip_prof.so MELD_KNN_FILTER_ABL=$a python tools/knn_only.py 1000000 3 2>&1 | grep "knn_filter" | tail -1; done
-    echo "## search over the thinned lists, timing-only ablations of the list kernel (MELD_KNN16_ABLATION: 1 = no selection, 8 = MFMAs only with tiles from an L2-hot set, 9 = MFMAs only without tile loads); knn_topk in ms"
-    for a in 1 8 9; do echo -n "abl $a: "; MELD_HIP_LIB=$PWD/meld_amd/libmeld_hip_prof.so MELD_KNN16_ABLATION=$a python tools/knn_only.py 1000000 3 2>&1 | grep "knn_filter" | tail -1; done
-  else echo "(no profiling build of the library in the tree: ablations skipped)"; fi
   echo "## d = 100 (the reference's default n_pca): 1M x 100, principal frame by the library rotation, the same two passes"
   DIMS=100 python tools/knn_only.py 1000000 3 2>&1 | grep -v amdgpu.ids | tail -3
   DIMS=100 MELD_KNN_ROTATE=0 python tools/knn_only.py 1000000 2 2>&1 | grep -v amdgpu.ids | tail -1

@@ -1,5 +1,5 @@
 """Time the candidate-search stage alone on the benchmark cells (in locality order, as in fit):
-python tools/knn_only.py N[,N...] [reps]      (env: MELD_KNN_* switches of HipOps, MELD_KNN16_ABLATION)"""
+python tools/knn_only.py N[,N...] [reps]      (env: MELD_KNN_* / MELD_KNN16_* switches of the plan, MELD_KNN16_STATS)"""
 import os
 import sys
 
