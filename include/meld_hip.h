@@ -325,6 +325,34 @@ int meld_knn_radius_exact(const double* X, int64_t N, int d, int64_t q_begin, co
 int meld_knn_pair_distances(const double* X, int d, const int64_t* rows, const int64_t* cand, int64_t n, int kk, double* out,
                             meld_stream_t stream);
 
+/* ---- exact kNN graph under the L1 / L-infinity metrics (replaces [UPSTREAM graphtools kNNGraph(distance="manhattan" |
+ *      "cityblock" | "l1" | "chebyshev") -> sklearn NearestNeighbors(metric=...)], reached from reference meld/meld.py:273;
+ *      csrc/metric_knn.hip) ------------------------------------------------------------------------
+ * Distances are fp64 in one arithmetic and one order for all four calls: |x_k - y_k| summed (L1) or maxed (L-inf) over
+ * k = 0 .. d - 1, starting at +0.  d <= 256, N < 2^31, rows in the order the caller gives (tiles = consecutive rows). */
+#define MELD_METRIC_L1 1
+#define MELD_METRIC_LINF 2
+int meld_metric_tile_rows(void); /* rows per tile (64) */
+/* box_lo / box_hi [ceil(N / 64)][d]: per-coordinate minimum / maximum of every tile of rows */
+int meld_metric_tile_boxes(const double* X, int64_t N, int d, double* box_lo, double* box_hi, meld_stream_t stream);
+/* Every row's ksel nearest rows by (distance, column), exactly, ascending: cand_idx / cand_d [N][ksel], cand_cnt[N] =
+ * min(ksel, N).  heap_d / heap_i: scratch of ksel * ceil(N / 64) * 64 entries each.  prune = 0 visits every tile (the
+ * result is the same bit for bit).  tiles_done[0] (zeroed by the caller) += (query tile, reference tile) pairs computed. */
+int meld_metric_topk(const double* X, int64_t N, int d, int metric, int ksel, const double* box_lo, const double* box_hi, int prune,
+                     double* heap_d, int32_t* heap_i, int32_t* cand_idx, double* cand_d, int32_t* cand_cnt,
+                     unsigned long long* tiles_done, meld_stream_t stream);
+/* meld_knn_refine's outputs from those lists: bw[N] = max((knn+1)-th distance, eps), cand_val[N][ksel] = kernel value or 0
+ * (diagonal and values below thresh dropped), keep_cnt[N]; a row whose full list does not reach beyond its kernel radius is
+ * appended to flag_rows (n_flag[0] zeroed by the caller) with keep_cnt 0.  decay = +inf: connectivity of d <= bw. */
+int meld_metric_refine(const int32_t* cand_idx, const double* cand_d, const int32_t* cand_cnt, int64_t N, int ksel, int knn,
+                       double decay, double thresh, double* bw, double* cand_val, int32_t* keep_cnt, int32_t* flag_rows,
+                       int32_t* n_flag, meld_stream_t stream);
+/* Exact sweep of the flagged rows over all N references (meld_knn_radius_exact's formats): mode 0 fb_cnt[f] (zeroed by the
+ * caller) = off-diagonal references with kernel value >= thresh; mode 1 writes them at fb_off[f] + fb_cursor[f] (zero on entry). */
+int meld_metric_radius(const double* X, int64_t N, int d, int metric, const int32_t* flag_rows, int32_t n_flag, const double* bw,
+                       double decay, double thresh, int mode, int32_t* fb_cnt, const int64_t* fb_off, int32_t* fb_cursor,
+                       int32_t* fb_col, double* fb_val, meld_stream_t stream);
+
 /* ---- symmetrise / anisotropy / Laplacian pieces (replaces [UPSTREAM graphtools
  *      BaseGraph.symmetrize_kernel, apply_anisotropy, PyGSPGraph._build_weight_from_kernel;
  *      pygsp Graph.compute_laplacian]) ------------------------------------------------------- */

@@ -18,6 +18,10 @@ MELD_REORDER            1           cache-locality permutation of the cells befo
 MELD_PINNED_RESULT      1           densities are handed to the caller in the pinned buffer they left the device through
 MELD_SHARDED_C_LOOPS    1           row-sharded recurrences enqueued from C on the library's own RCCL communicator
 =====================  ==========  =======================================================================================
+
+Development switches are read where they are used, through ``opt``; among them ``MELD_METRIC_PRUNE`` (default 1; 0: the L1 /
+L-infinity candidate search of ``meld_amd.metric_knn`` visits every tile instead of skipping those its box bound rules out --
+the same graph bit for bit, for A-B measurements and tests).
 """
 import os
 

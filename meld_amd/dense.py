@@ -156,10 +156,13 @@ def build_dense_knn_graph(X, knn, decay, thresh, anisotropy=1, symm=(0, 0.0), me
                                   "N <= {}".format(knn, metric, DENSE_MAX_N))
     knn = min(int(knn), N - 2)
     X = X.to(torch.float64)
+    # (in blocks of rows: the library's pairwise-distance kernel launches a thread block per pair, and beyond 2^32 threads in one
+    # launch -- 4096^2 pairs -- the rows at the end came out wrong, 54 off at 8000 cells; each pair's arithmetic is unchanged)
+    rows = max(1, (1 << 23) // max(N, 1))
     if metric in ("euclidean", "l2"):
-        D = torch.cdist(X, X, p=2.0, compute_mode="donot_use_mm_for_euclid_dist")
+        D = torch.cat([torch.cdist(X[i : i + rows], X, p=2.0, compute_mode="donot_use_mm_for_euclid_dist") for i in range(0, N, rows)])
     else:
-        D = torch.cdist(X, X, p=_CDIST_P[metric])
+        D = torch.cat([torch.cdist(X[i : i + rows], X, p=_CDIST_P[metric]) for i in range(0, N, rows)])
     D.fill_diagonal_(0.0)
     K, bw = _alpha_decay_dense(D, knn, decay, max(float(thresh), float(np.finfo(float).eps)))
     return _graph_from_dense_kernel(K, anisotropy, bw, dict(knn=int(knn), dense_knn=True, metric=metric), symm=symm)

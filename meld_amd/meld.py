@@ -206,11 +206,19 @@ class MELD(GraphEstimator):
 
         if str(self.distance).lower() in ("manhattan", "cityblock", "l1", "chebyshev"):
             # metrics that are no function of the euclidean distance of transformed rows: the matrix pipe's search does not apply;
-            # the same kernel on library pairwise distances, densely, up to DENSE_MAX_N cells
+            # the same kernel on library pairwise distances, densely, up to DENSE_MAX_N cells, and beyond that the exact L1 / L-inf
+            # search of meld_amd.metric_knn
             from .dense import build_dense_knn_graph
+            from .metric_knn import build_metric_knn_graph, metric_route
 
-            if any(opts.get(k) is not None for k in ("sample_idx", "bandwidth", "bandwidth_scale", "knn_max")) or (self.thresh == 0 and self.decay is not None):
-                raise NotImplementedError("distance={!r} is implemented for the plain alpha-decay / unweighted kNN graph only".format(self.distance))
+            try:
+                route = metric_route(int(X.shape[0]), int(X.shape[1]), self.knn, self.decay, self.thresh, opts)
+            except NotImplementedError:
+                raise NotImplementedError("distance={!r} is implemented for the plain alpha-decay / unweighted kNN graph only".format(self.distance)) from None
+            if route == "metric_knn":
+                return build_metric_knn_graph(X, self.knn, self.decay, self.thresh, self.anisotropy, str(self.distance).lower(),
+                                              kernel_symm=opts.get("kernel_symm", "+"), theta=opts.get("theta"), ksel=opts.get("ksel"),
+                                              profile=bool(opts.get("profile", False)), ops=ops0)
             return build_dense_knn_graph(X, self.knn, self.decay, self.thresh, anisotropy=self.anisotropy, symm=symm, metric=str(self.distance).lower())
         # (the metric enters through the data: cosine = the euclidean graph of the unit rows with the decay doubled)
         X, decay_m, bw_to_metric = metric_front_end(X, self.distance, self.decay)
