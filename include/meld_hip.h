@@ -122,6 +122,14 @@ int meld_knn16_prepare(const double* X, int64_t N, int d, const double* mean, in
 int meld_knn16_prepare_scaled(const double* X, int64_t N, int d, const double* mean, const double* col_min, const double* col_max,
                               int64_t q_begin, int64_t q_count, void* Rt16, void* Q16, float* Qn, float* norm2, float* norm2_max,
                               float* scale_info, meld_stream_t stream);
+/* Queries = all N references (q_begin = 0, q_count = N: every single-GPU build): the operands of meld_knn16_prepare_scaled (of
+ * meld_knn16_prepare where col_min and col_max are both NULL) AND the tile spheres of meld_knn16_tile_spheres over all tiles, in
+ * temp (meld_knn16_bounds_temp_bytes bytes, zeroed inside), from ONE pass over X: every 64-row tile is read once and written in
+ * both layouts, its sphere computed from the same copy in LDS.  Bit-identical to the separate calls.  Afterwards
+ * meld_knn16_step_lists_direct_spheres / meld_knn16_bounds_from_spheres take the spheres from temp. */
+int meld_knn16_prepare_fused(const double* X, int64_t N, int d, const double* mean, const double* col_min, const double* col_max,
+                             void* Rt16, void* Q16, float* Qn, float* norm2, float* norm2_max, float* scale_info, void* temp,
+                             meld_stream_t stream);
 /* Optional exact pruning.  meld_knn16_bounds fills lb2[n_query_waves][n_tiles] (fp16, rounded towards
  * zero) with a lower bound (scaled space) on the squared distance between any query of a wave of the
  * search kernel (64 consecutive cells = one reference tile) and any reference of a tile (TS consecutive
@@ -234,6 +242,10 @@ int meld_knn16_step_lists_direct(const double* X, int64_t N, int d, const double
 /* ... with the bounds taken from the first K block of the operands alone (lead_only != 0; SPLIT layout, cells in a frame whose
  * leading coordinates carry the distances -- see meld_knn16_split_dims): lower bounds all the same, a quarter of the tile stream. */
 int meld_knn16_step_lists_direct_lead(const double* X, int64_t N, int d, const double* mean, const float* scale_info, const float* norm2_max,
+                                 const void* Rt16, const float* thr_seed, const float* q_norm2, int nprod, void* temp, void* scratch,
+                                 uint32_t* list, int64_t list_stride, int32_t* cnt, int lead_only, meld_stream_t stream);
+/* meld_knn16_step_lists_direct_lead with the tile spheres already in temp (meld_knn16_prepare_fused): X and mean are not read. */
+int meld_knn16_step_lists_direct_spheres(const double* X, int64_t N, int d, const double* mean, const float* scale_info, const float* norm2_max,
                                  const void* Rt16, const float* thr_seed, const float* q_norm2, int nprod, void* temp, void* scratch,
                                  uint32_t* list, int64_t list_stride, int32_t* cnt, int lead_only, meld_stream_t stream);
 int meld_knn16_topk_listed(const void* Q16, const float* Qn, const void* Rt16, const float* scale_info, int64_t n_ref, int d,
@@ -418,6 +430,15 @@ int meld_csr_rows_sort_merge(const int32_t* cursor, int64_t n_rows, int32_t* tco
                              int32_t* flags,
                              int symm /* how K and K^T combine [UPSTREAM graphtools kernel_symm]: 0 "+" (K + K^T) / 2, 1 "*" K o K^T, 2 "mnn" */,
                              double theta /* symm 2: theta min(K, K^T) + (1 - theta) max(K, K^T) */, meld_stream_t stream);
+/* meld_csr_rows_sort_merge, and sums[r] = diag + the merged row's sum out of the wave that holds the row: bit for bit what
+ * meld_csr_compact_rows_sums returns (valid where no flag is set). */
+int meld_csr_rows_sort_merge_sums(const int32_t* cursor, int64_t n_rows, int32_t* tcol, double* tval, int32_t* ucnt, int32_t* flags,
+                                  int symm, double theta, double diag, double* sums, meld_stream_t stream);
+/* The compaction with the anisotropy applied on the way out and the degrees of the result: col / val / dw equal, bit for bit,
+ * meld_csr_compact_rows followed by meld_csr_anisotropy_degrees(ksum, offset 0).  n_rows = all rows of the graph (the columns
+ * index ksum, the sums of meld_csr_rows_sort_merge_sums); anisotropy 0: the plain copy. */
+int meld_csr_compact_rows_anisotropy(const int64_t* rowptr, int64_t n_rows, const int32_t* tcol, const double* tval, int32_t* col,
+                                     double* val, const double* ksum, double anisotropy, double* dw, meld_stream_t stream);
 int meld_csr_compact_rows(const int64_t* rowptr, int64_t n_rows, const int32_t* tcol, const double* tval,
                           int32_t* col, double* val, meld_stream_t stream);
 /* The same, and sums[r] = diag + the row's sum on the way out: bit for bit what meld_csr_row_sums returns for the compacted rows. */

@@ -493,7 +493,7 @@ __device__ __forceinline__ void csr_bitonic_sort(K (&key)[SL], int lane) {
 // All three are symmetric functions of the pair, so W stays bitwise symmetric.
 template <int SL>
 __device__ __forceinline__ int csr_row_merge(int* __restrict__ tcol, double* __restrict__ tval, int64_t base, int n, int lane,
-                                             bool* bad, int symm, double theta) {
+                                             bool* bad, int symm, double theta, double* srow) {
   // keys (column : slot), slot < CSR_BUCKET = 2^8.  Columns below 2^24 - 1 -- every graph of fewer than 16.7 M cells -- fit a 32-bit
   // key with the slot: the network then compares and selects single words (the kernel is bound by the vector instructions of
   // its compare-exchanges, not by the exchanges themselves); same order, same result.  Decided per row, wave-uniformly.
@@ -591,6 +591,7 @@ __device__ __forceinline__ int csr_row_merge(int* __restrict__ tcol, double* __r
     if (is_head[e]) {
       tcol[base + head_pos[e]] = (int)head_col[e];
       tval[base + head_pos[e]] = head_val[e];
+      if (srow != nullptr) srow[head_pos[e]] = head_val[e];  // (the merged row for the wave's sum: csr_rows_sort_merge_kernel)
     }
   }
   if (__any(any_bad)) *bad = true;
@@ -599,7 +600,12 @@ __device__ __forceinline__ int csr_row_merge(int* __restrict__ tcol, double* __r
 
 __global__ __launch_bounds__(256) void csr_rows_sort_merge_kernel(const int* __restrict__ cursor, int64_t n_rows,
                                                                   int* __restrict__ tcol, double* __restrict__ tval,
-                                                                  int* __restrict__ ucnt, int* __restrict__ flags, int symm, double theta) {
+                                                                  int* __restrict__ ucnt, int* __restrict__ flags, int symm, double theta,
+                                                                  double diag, double* __restrict__ sums) {
+  // sums (optional): sums[r] = diag + the merged row's sum, added as csr_compact_rows_sums_kernel adds it -- lane g of eight
+  // takes entries g, g + 8, ..., then the three exchanges -- from the wave's copy of the row in LDS
+  __shared__ double s_rows[4][CSR_BUCKET];
+  double* srow = sums != nullptr ? s_rows[threadIdx.x >> 6] : nullptr;
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= n_rows) return;
@@ -615,14 +621,24 @@ __global__ __launch_bounds__(256) void csr_rows_sort_merge_kernel(const int* __r
   bool bad = false;
   int total;
   if (n <= 64)
-    total = csr_row_merge<1>(tcol, tval, base, n, lane, &bad, symm, theta);
+    total = csr_row_merge<1>(tcol, tval, base, n, lane, &bad, symm, theta, srow);
   else if (n <= 128)
-    total = csr_row_merge<2>(tcol, tval, base, n, lane, &bad, symm, theta);
+    total = csr_row_merge<2>(tcol, tval, base, n, lane, &bad, symm, theta, srow);
   else
-    total = csr_row_merge<4>(tcol, tval, base, n, lane, &bad, symm, theta);
+    total = csr_row_merge<4>(tcol, tval, base, n, lane, &bad, symm, theta, srow);
   if (lane == 0) {
     ucnt[r] = total;
     if (bad) atomicOr(flags, 2);
+  }
+  if (sums != nullptr) {  // (uniform)
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // (one wave: its LDS stores precede its loads)
+    double s = 0.0;
+    if (lane < 8)
+      for (int k = lane; k < total; k += 8) s += srow[k];
+    s += __shfl_xor(s, 1, 64);
+    s += __shfl_xor(s, 2, 64);
+    s += __shfl_xor(s, 4, 64);
+    if (lane == 0) sums[r] = diag + s;
   }
 }
 
@@ -665,6 +681,53 @@ __global__ __launch_bounds__(256) void csr_compact_rows_sums_kernel(const int64_
   s += __shfl_xor(s, 2, 64);
   s += __shfl_xor(s, 4, 64);
   if (r < n_rows && g == 0) sums[r] = diag + s;
+}
+
+// The compaction with the anisotropy on the way out: val = K_ij / (ksum_i ksum_j)^a and dw[r] = the row's sum of the result, the
+// expression and the order of additions of csr_anisotropy_kernel (a = 0: the copy, and the sums of csr_row_sums_kernel with diag 0),
+// so the pass that read the CSR back a launch later is gone without moving a bit.  ksum: the kernel's row sums of ALL rows
+// (csr_rows_sort_merge_kernel's), columns index it.
+__global__ __launch_bounds__(256) void csr_compact_rows_anisotropy_kernel(const int64_t* __restrict__ rowptr, int64_t n_rows,
+                                                                          const int* __restrict__ tcol, const double* __restrict__ tval,
+                                                                          int* __restrict__ col, double* __restrict__ val,
+                                                                          const double* __restrict__ ksum, double anisotropy,
+                                                                          double* __restrict__ dw) {
+  const int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 3;
+  const int g = threadIdx.x & 7;
+  double s = 0.0;
+  if (r < n_rows) {
+    const double di = ksum[r];
+    const int64_t src = r * CSR_BUCKET, dst = rowptr[r];
+    const int len = (int)(rowptr[r + 1] - dst);
+    constexpr int U = 4;
+    for (int k0 = g; k0 < len; k0 += 8 * U) {
+      int c[U];
+      double v[U], kj[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int k = k0 + 8 * u;
+        c[u] = k < len ? tcol[src + k] : 0;
+        v[u] = k < len ? tval[src + k] : 0.0;
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) kj[u] = ksum[c[u]];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        const int k = k0 + 8 * u;
+        if (k < len) {
+          const double dd = di * kj[u];
+          const double w = (anisotropy == 0.0) ? v[u] : (anisotropy == 1.0) ? v[u] / dd : v[u] / pow(dd, anisotropy);
+          col[dst + k] = c[u];
+          val[dst + k] = w;
+          s += w;
+        }
+      }
+    }
+  }
+  s += __shfl_xor(s, 1, 64);
+  s += __shfl_xor(s, 2, 64);
+  s += __shfl_xor(s, 4, 64);
+  if (r < n_rows && g == 0) dw[r] = 0.0 + s;
 }
 
 extern "C" int meld_csr_bucket_slots(void) { return CSR_BUCKET; }
@@ -725,8 +788,35 @@ extern "C" int meld_csr_rows_sort_merge(const int32_t* cursor, int64_t n_rows, i
                  "meld_csr_rows_sort_merge: symm must be 0 (+), 1 (*) or 2 (mnn, theta in [0, 1])");
   MELD_HIP_CALL(hipMemsetAsync(flags, 0, sizeof(int32_t), S(stream)));
   hipLaunchKernelGGL(csr_rows_sort_merge_kernel, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, S(stream), cursor, n_rows,
-                     tcol, tval, ucnt, flags, symm, theta);
+                     tcol, tval, ucnt, flags, symm, theta, 0.0, (double*)nullptr);
   MELD_LAUNCH_CHECK("csr_rows_sort_merge_kernel");
+  return MELD_OK;
+}
+
+// The same, and sums[r] = diag + the merged row's sum: bit for bit what meld_csr_compact_rows_sums returns for the row (rows of a
+// build that sets a flag hold nothing to rely on).
+extern "C" int meld_csr_rows_sort_merge_sums(const int32_t* cursor, int64_t n_rows, int32_t* tcol, double* tval, int32_t* ucnt,
+                                             int32_t* flags, int symm, double theta, double diag, double* sums, meld_stream_t stream) {
+  MELD_CHECK_ARG(cursor && tcol && tval && ucnt && flags && sums && n_rows > 0, "meld_csr_rows_sort_merge_sums: bad arguments");
+  MELD_CHECK_ARG(symm >= 0 && symm <= 2 && (symm != 2 || (theta >= 0.0 && theta <= 1.0)),
+                 "meld_csr_rows_sort_merge_sums: symm must be 0 (+), 1 (*) or 2 (mnn, theta in [0, 1])");
+  MELD_HIP_CALL(hipMemsetAsync(flags, 0, sizeof(int32_t), S(stream)));
+  hipLaunchKernelGGL(csr_rows_sort_merge_kernel, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, S(stream), cursor, n_rows,
+                     tcol, tval, ucnt, flags, symm, theta, diag, sums);
+  MELD_LAUNCH_CHECK("csr_rows_sort_merge_kernel");
+  return MELD_OK;
+}
+
+// The merged buckets -> CSR with the anisotropy applied and the degrees of the result (n_rows = ALL rows of the graph: ksum, from
+// meld_csr_rows_sort_merge_sums, is indexed by column): col / val / dw equal, bit for bit, meld_csr_compact_rows followed by
+// meld_csr_anisotropy_degrees(ksum, offset 0).
+extern "C" int meld_csr_compact_rows_anisotropy(const int64_t* rowptr, int64_t n_rows, const int32_t* tcol, const double* tval,
+                                                int32_t* col, double* val, const double* ksum, double anisotropy, double* dw,
+                                                meld_stream_t stream) {
+  MELD_CHECK_ARG(rowptr && n_rows > 0 && tcol && tval && col && val && ksum && dw, "meld_csr_compact_rows_anisotropy: bad arguments");
+  hipLaunchKernelGGL(csr_compact_rows_anisotropy_kernel, dim3((unsigned)ceil_div(n_rows * 8, 256)), dim3(256), 0, S(stream), rowptr, n_rows,
+                     tcol, tval, col, val, ksum, anisotropy, dw);
+  MELD_LAUNCH_CHECK("csr_compact_rows_anisotropy_kernel");
   return MELD_OK;
 }
 

@@ -1422,28 +1422,13 @@ __global__ __launch_bounds__(64) void knn16_merge_slices_kernel(const int* __res
 // ---------------------------------------------------------------------------------------------
 // One workgroup per reference tile: centroid (scaled fp32) written as a query-operand row
 // ([kb][h][plane][8], 1.0 in K slots d .. d+2), its squared norm, and the tile radius.
-__global__ __launch_bounds__(256) void tile_spheres_kernel(const double* __restrict__ X, int64_t N, int d,
-                                                           const double* __restrict__ mean,
-                                                           const float* __restrict__ scale_info, int KB,
-                                                           _Float16* __restrict__ cent16, float* __restrict__ cent_n,
-                                                           float* __restrict__ cent_r, int tile0, int dA) {
-  // the tile's cells, row stride ld = d | 1 floats (odd: conflict-free column walks; sized by d, not by the largest d the
-  // library takes -- 13 KB instead of 37 at d = 50, three times the workgroups per CU of a kernel that is all latency)
-  extern __shared__ float xs_dyn[];
-  const int ld = d | 1;
+// The sphere of the tile whose `cnt` cells (scaled, centred fp32) the workgroup holds in LDS at xs_dyn, row stride ld floats; the
+// caller's barrier stands between the loads and this.  Rows cnt .. K16_TS - 1 are never read.
+__device__ __forceinline__ void k16_tile_sphere(const float* xs_dyn, int ld, int cnt, int d, int KB, int dA, int tile,
+                                                _Float16* __restrict__ cent16, float* __restrict__ cent_n, float* __restrict__ cent_r) {
 #define XS(r, k) xs_dyn[(r) * ld + (k)]
   __shared__ float cs[K16_DMAX + 19];
   const int tid = threadIdx.x;
-  const int tile = tile0 + (int)blockIdx.x;  // (a row-sharded build computes the spheres of a range of tiles per rank)
-  const int64_t row0 = (int64_t)tile * K16_TS;
-  const int cnt = (int)min((int64_t)K16_TS, N - row0);
-  const float s = scale_info[0];
-  for (int u = tid; u < K16_TS * d; u += 256) {
-    const int r = u / d, k = u - r * d;
-    const int64_t i = row0 + r;
-    XS(r, k) = i < N ? s * (float)(X[i * d + k] - mean[k]) : 0.0f;
-  }
-  __syncthreads();
   if (tid < KB * 16) {
     float acc = 0.0f;
     if (tid < d)
@@ -1545,6 +1530,29 @@ __global__ __launch_bounds__(256) void tile_spheres_kernel(const double* __restr
     qrow[g * 2 + 1] = lo;
   }
 #undef XS
+}
+
+__global__ __launch_bounds__(256) void tile_spheres_kernel(const double* __restrict__ X, int64_t N, int d,
+                                                           const double* __restrict__ mean,
+                                                           const float* __restrict__ scale_info, int KB,
+                                                           _Float16* __restrict__ cent16, float* __restrict__ cent_n,
+                                                           float* __restrict__ cent_r, int tile0, int dA) {
+  // the tile's cells, row stride ld = d | 1 floats (odd: conflict-free column walks; sized by d, not by the largest d the
+  // library takes -- 13 KB instead of 37 at d = 50, three times the workgroups per CU of a kernel that is all latency)
+  extern __shared__ float xs_dyn[];
+  const int ld = d | 1;
+  const int tid = threadIdx.x;
+  const int tile = tile0 + (int)blockIdx.x;  // (a row-sharded build computes the spheres of a range of tiles per rank)
+  const int64_t row0 = (int64_t)tile * K16_TS;
+  const int cnt = (int)min((int64_t)K16_TS, N - row0);
+  const float s = scale_info[0];
+  for (int u = tid; u < K16_TS * d; u += 256) {
+    const int r = u / d, k = u - r * d;
+    const int64_t i = row0 + r;
+    xs_dyn[r * ld + k] = i < N ? s * (float)(X[i * d + k] - mean[k]) : 0.0f;
+  }
+  __syncthreads();
+  k16_tile_sphere(xs_dyn, ld, cnt, d, KB, dA, tile, cent16, cent_n, cent_r);
 }
 
 // Workgroup = 256 centroids (4 waves x 2 groups of 32, B fragments, hi parts) x a slice of the query
@@ -1911,6 +1919,120 @@ __global__ __launch_bounds__(256) void prepare16_kernel(const double* __restrict
   }
 }
 
+// Queries = all the references (every single-GPU build): ONE read of a tile's 64 rows gives the tile in Rt layout, the same rows
+// in Q layout with Qn, norm2 and norm2_max, and the tile's sphere -- prepare16_kernel<true>, prepare16_kernel<false> and
+// tile_spheres_kernel on the same rows, each value from the same operations in the same order (tests/test_gpu_fused_operands.py
+// compares the bytes).  The rows are loaded as queries (rows behind N repeat the last one); as references the rows behind N
+// count as zeros, the sphere never looks at them.  Workgroups behind the last reference tile pad the queries to a whole block.
+__global__ __launch_bounds__(256) void prepare16_fused_kernel(const double* __restrict__ X, int64_t N, int d,
+                                                              const double* __restrict__ mean,
+                                                              const float* __restrict__ scale_info, int KB,
+                                                              _Float16* __restrict__ Rt16, _Float16* __restrict__ Q16,
+                                                              float* __restrict__ Qn, float* __restrict__ norm2,
+                                                              float* __restrict__ norm2_max, _Float16* __restrict__ cent16,
+                                                              float* __restrict__ cent_n, float* __restrict__ cent_r, int n_t, int dA) {
+  extern __shared__ float xs_dyn[];  // row stride d | 1 floats, as in tile_spheres_kernel
+  const int ld = d | 1;
+#define XS(r, k) xs_dyn[(r) * ld + (k)]
+  const int tid = threadIdx.x;
+  const int64_t row0 = (int64_t)blockIdx.x * K16_TS;
+  const float s = scale_info[0];
+  for (int u = tid; u < K16_TS * d; u += 256) {
+    const int r = u / d, k = u - r * d;
+    const int64_t src = row0 + r < N ? row0 + r : N - 1;
+    XS(r, k) = s * (float)(X[src * d + k] - mean[k]);
+  }
+  __syncthreads();
+  const int r = tid & 63, part = tid >> 6;
+  const int64_t i = row0 + r;
+  const bool is_tile = (int)blockIdx.x < n_t;  // (uniform)
+  const bool real = i < N;
+  float n = 0.0f;
+  for (int k = 0; k < d; ++k) n = fmaf(XS(r, k), XS(r, k), n);
+  // the norm pieces of the reference (see prepare16_kernel)
+  float nA = 0.0f, nB = real ? n : INFINITY;
+  if (is_tile && dA > 0) {
+    nB = 0.0f;
+    for (int k = 0; k < dA; ++k) nA = fmaf(XS(r, k), XS(r, k), nA);
+    for (int k = dA; k < d; ++k) nB = fmaf(XS(r, k), XS(r, k), nB);
+    const float m_r = 1.03f * 0.0009765625f * nB + (float)d * 2.384185791015625e-07f;
+    nA -= m_r;
+    nB += m_r;
+    if (!real) {
+      nA = INFINITY;
+      nB = 0.0f;
+    }
+  }
+  _Float16 npc[6];
+  {
+    const float src2[2] = {nA, nB};
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const float nn = src2[q];
+      const _Float16 n1 = (_Float16)nn;
+      const float r1 = isinf(nn) ? 0.0f : nn - (float)n1;
+      const _Float16 n2 = (_Float16)r1;
+      npc[3 * q + 0] = n1;
+      npc[3 * q + 1] = n2;
+      npc[3 * q + 2] = (_Float16)(r1 - (float)n2);
+    }
+  }
+  for (int g = part; g < KB * 2; g += 4) {
+    f16x8 qhi, qlo, rhi, rlo;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      int cc, pc;
+      k16_slot(g * 8 + e, d, dA, &cc, &pc);
+      _Float16 qh = (_Float16)0.0f, ql = (_Float16)0.0f, rh = (_Float16)0.0f, rl = (_Float16)0.0f;
+      if (cc >= 0) {
+        const float vq = XS(r, cc);
+        qh = (_Float16)vq;
+        ql = (_Float16)(vq - (float)qh);
+        // (the reference's pieces from a value the compiler cannot relate to the query's: derived from qh, a zero coordinate came
+        // out as (+0, -0) where prepare16_kernel<true> writes (-0, +0))
+        float xr = real ? vq : 0.0f;
+        asm volatile("" : "+v"(xr));
+        const float vr = -2.0f * xr;
+        rh = (_Float16)vr;
+        rl = (_Float16)(vr - (float)rh);
+      } else if (pc >= 0) {
+        qh = (_Float16)1.0f;
+        rh = npc[pc];
+      }
+      qhi[e] = qh;
+      qlo[e] = ql;
+      rhi[e] = rh;
+      rlo[e] = rl;
+    }
+    f16x8* qrow = reinterpret_cast<f16x8*>(Q16) + (size_t)i * ((size_t)KB * 4);
+    qrow[g * 2 + 0] = qhi;
+    qrow[g * 2 + 1] = qlo;
+    if (is_tile) {
+      f16x8* tile = reinterpret_cast<f16x8*>(Rt16) + (size_t)blockIdx.x * ((size_t)KB * 2 * 2 * K16_TS);
+      tile[(size_t)(g * 2 + 0) * K16_TS + r] = rhi;
+      tile[(size_t)(g * 2 + 1) * K16_TS + r] = rlo;
+    }
+  }
+  if (part == 0) {
+    Qn[i] = n;
+    if (is_tile) {
+      float n_orig = 0.0f;
+      if (real) {
+        n_orig = n * scale_info[1];
+        norm2[i] = n_orig;
+      }
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) n_orig = fmaxf(n_orig, __shfl_xor(n_orig, off, 64));
+      if (r == 0) atomicMax(reinterpret_cast<int*>(norm2_max), __float_as_int(n_orig));
+    }
+  }
+#undef XS
+  if (is_tile) {
+    const int cnt = (int)min((int64_t)K16_TS, N - row0);
+    k16_tile_sphere(xs_dyn, ld, cnt, d, KB, dA, (int)blockIdx.x, cent16, cent_n, cent_r);
+  }
+}
+
 // Threshold seeds.  The scan starts with every threshold at +inf, so the first tiles of a workgroup -- its own
 // 256 cells -- are appended wholesale (256 appends and ~3 compactions per row, a third of what learning the
 // thresholds costs the search).  A valid start value is cheap: the (knn+1)-th smallest distance of a cell among the cells
@@ -2176,6 +2298,39 @@ extern "C" int meld_knn16_prepare_scaled(const double* X, int64_t N, int d, cons
                                          float* scale_info, meld_stream_t stream) {
   MELD_CHECK_ARG(col_min && col_max, "meld_knn16_prepare_scaled: null column extremes");
   return k16_prepare_impl(X, N, d, mean, q_begin, q_count, Rt16, Q16, Qn, norm2, norm2_max, scale_info, stream, col_min, col_max);
+}
+
+// Queries = all N references: the operands of meld_knn16_prepare[_scaled](q_begin = 0, q_count = N) AND the tile spheres of
+// meld_knn16_tile_spheres over all tiles (temp: meld_knn16_bounds_temp_bytes bytes, zeroed here) from one pass over X, bit for
+// bit.  col_min / col_max: both or neither (neither: the scale from a pass of its own, as meld_knn16_prepare).
+extern "C" int meld_knn16_prepare_fused(const double* X, int64_t N, int d, const double* mean, const double* col_min, const double* col_max,
+                                        void* Rt16, void* Q16, float* Qn, float* norm2, float* norm2_max, float* scale_info, void* temp,
+                                        meld_stream_t stream) {
+  MELD_CHECK_ARG(X && mean && Rt16 && Q16 && Qn && norm2 && norm2_max && scale_info && temp && N > 0,
+                 "meld_knn16_prepare_fused: null/empty argument");
+  MELD_CHECK_ARG((col_min == nullptr) == (col_max == nullptr), "meld_knn16_prepare_fused: column minima and maxima go together");
+  const int KB = meld_knn16_kblocks(d);
+  if (KB < 0) return KB;
+  hipStream_t st = S(stream);
+  MELD_HIP_CALL(hipMemsetAsync(scale_info, 0, 4 * sizeof(float), st));
+  MELD_HIP_CALL(hipMemsetAsync(norm2_max, 0, sizeof(float), st));
+  if (col_min != nullptr)
+    hipLaunchKernelGGL(absmax_from_extremes_kernel, dim3(1), dim3(256), 0, st, mean, col_min, col_max, d, scale_info);
+  else
+    hipLaunchKernelGGL(absmax_centered_kernel, dim3(2048), dim3(256), 0, st, X, N * (int64_t)d, d, mean, scale_info);
+  hipLaunchKernelGGL(finish_scale_kernel, dim3(1), dim3(1), 0, st, scale_info);
+  const int n_t = (int)ceil_div(N, K16_TS);
+  const size_t n_c = (size_t)ceil_div(n_t, K16_BOUNDS_THREADS) * K16_BOUNDS_THREADS;
+  _Float16* c16 = reinterpret_cast<_Float16*>(temp);
+  float* cn = reinterpret_cast<float*>(reinterpret_cast<char*>(temp) + n_c * (size_t)KB * 64);
+  float* cr = cn + n_c;
+  MELD_HIP_CALL(hipMemsetAsync(temp, 0, n_c * ((size_t)KB * 64 + 2 * sizeof(float)), st));
+  const int64_t q_pad = ceil_div(N, K16_BQ) * K16_BQ;
+  hipLaunchKernelGGL(prepare16_fused_kernel, dim3((unsigned)(q_pad / K16_TS)), dim3(256), sizeof(float) * K16_TS * (size_t)(d | 1), st, X, N, d,
+                     mean, scale_info, KB, reinterpret_cast<_Float16*>(Rt16), reinterpret_cast<_Float16*>(Q16), Qn, norm2, norm2_max, c16, cn, cr,
+                     n_t, k16_dA(d, KB));
+  MELD_LAUNCH_CHECK("meld_knn16_prepare_fused");
+  return MELD_OK;
 }
 
 // The same for a search between two point sets (the blocks of graphtools' MNN kernel between two samples): X holds
@@ -2605,7 +2760,7 @@ extern "C" size_t meld_knn16_list_scratch_bytes(int64_t n_ref) {
 static int k16_step_lists_direct_impl(const double* X, int64_t N, int d, const double* mean, const float* scale_info,
                                       const float* norm2_max, const void* Rt16, const float* thr_seed, const float* q_norm2,
                                       int nprod, void* temp, void* scratch, uint32_t* list, int64_t list_stride, int32_t* cnt,
-                                      int lead_only, meld_stream_t stream) {
+                                      int lead_only, meld_stream_t stream, bool spheres_ready = false) {
   MELD_CHECK_ARG(nprod == 1 || nprod == 3, "meld_knn16_step_lists_direct: nprod must be 1 or 3");
   MELD_CHECK_ARG(X && mean && scale_info && norm2_max && Rt16 && thr_seed && q_norm2 && temp && scratch && list && cnt && N > 0,
                  "meld_knn16_step_lists_direct: bad arguments");
@@ -2623,8 +2778,10 @@ static int k16_step_lists_direct_impl(const double* X, int64_t N, int d, const d
   unsigned long long* bits_a = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(scratch) + (((size_t)n_q * sizeof(float) + 255) / 256) * 256);
   unsigned long long* bits_b = bits_a + (size_t)n_q * wpr;
   unsigned long long* live = bits_b + (size_t)n_q * wpr;
-  MELD_HIP_CALL(hipMemsetAsync(temp, 0, n_c * ((size_t)KB * 64 + 2 * sizeof(float)), st));
-  hipLaunchKernelGGL(tile_spheres_kernel, dim3(n_t), dim3(256), sizeof(float) * K16_TS * (size_t)(d | 1), st, X, N, d, mean, scale_info, KB, c16, cn, cr, 0, k16_dA(d, KB));
+  if (!spheres_ready) {
+    MELD_HIP_CALL(hipMemsetAsync(temp, 0, n_c * ((size_t)KB * 64 + 2 * sizeof(float)), st));
+    hipLaunchKernelGGL(tile_spheres_kernel, dim3(n_t), dim3(256), sizeof(float) * K16_TS * (size_t)(d | 1), st, X, N, d, mean, scale_info, KB, c16, cn, cr, 0, k16_dA(d, KB));
+  }
   const float es = (float)meld_knn16_error_coef(nprod, d);
   hipLaunchKernelGGL(knn16_wave_thresholds_kernel, dim3((unsigned)ceil_div(n_q, 4)), dim3(256), 0, st, thr_seed, N, n_q, es, norm2_max,
                      scale_info, wthr);
@@ -2693,6 +2850,16 @@ extern "C" int meld_knn16_step_lists_direct_lead(const double* X, int64_t N, int
                                                  int lead_only, meld_stream_t stream) {
   return k16_step_lists_direct_impl(X, N, d, mean, scale_info, norm2_max, Rt16, thr_seed, q_norm2, nprod, temp, scratch, list, list_stride, cnt,
                                     lead_only, stream);
+}
+
+// The same with the tile spheres already in temp (meld_knn16_prepare_fused, or meld_knn16_tile_spheres over all tiles): X and mean
+// are not read.
+extern "C" int meld_knn16_step_lists_direct_spheres(const double* X, int64_t N, int d, const double* mean, const float* scale_info,
+                                                    const float* norm2_max, const void* Rt16, const float* thr_seed, const float* q_norm2,
+                                                    int nprod, void* temp, void* scratch, uint32_t* list, int64_t list_stride, int32_t* cnt,
+                                                    int lead_only, meld_stream_t stream) {
+  return k16_step_lists_direct_impl(X, N, d, mean, scale_info, norm2_max, Rt16, thr_seed, q_norm2, nprod, temp, scratch, list, list_stride, cnt,
+                                    lead_only, stream, true);
 }
 
 // Start values for the thresholds of meld_knn16_topk's first pass (thr_init, scaled units, roundup(q_count, BQ) floats) from

@@ -557,7 +557,8 @@ class HipOps:
 
     # ---- A2 + A3: directed alpha-decay kernel rows of [q_begin, q_begin + q_count) as COO -------
     def directed_kernel_coo(self, X, q_begin, q_count, knn, decay, thresh, ksel, tm=None, force_fallback=False, n_refs=None, assemble=False, comm=None,
-                            bw_scale=1.0, bw_fixed=None, col_stats=None, knn_max=None, symm=(0, 0.0), count_rows_ge=None, frame_axes=None):
+                            bw_scale=1.0, bw_fixed=None, col_stats=None, knn_max=None, symm=(0, 0.0), count_rows_ge=None, frame_axes=None,
+                            anisotropy=None):
         """Returns (keys[2M] int64, vals[2M] fp64, info): slot e < M holds (i, j, K_ij / 2) with
         key = i << 32 | j for the local row i; slot M + e holds the transposed (j, i, K_ij / 2).
 
@@ -573,6 +574,9 @@ class HipOps:
         ``knn_max``]): a row keeps its knn_max nearest cells (besides itself) at most.  ``count_rows_ge``: report the number of rows
         whose kernel radius holds at least that many cells, self counted (``info["rows_with_at_least"]``: what graphtools'
         re-search loop branches on, see ``build_knn_graph``).
+
+        ``anisotropy`` (with ``assemble``): the rows leave their buckets with the anisotropy applied and their degrees summed
+        (``info["assembled"]`` then ends with the kernel row sums and the degrees).
 
         The route (search back end, frame, seeds, pruning, lists, slices, filter pass) is ``meld_amd.knn_plan.plan_knn_search``'s;
         the stages run in this order: search operands, start thresholds, step lists, candidate search, refinement (+ the
@@ -595,7 +599,7 @@ class HipOps:
             retry_from, ksel = (ksel, r.n_flag), 128
             r = self._search_and_refine(a, ksel, None)
         s = self._exact_sweep(a, r, count_rows_ge)
-        keys, vals, assembled = self._emit(a, r, s, ksel, assemble, symm)
+        keys, vals, assembled = self._emit(a, r, s, ksel, assemble, symm, anisotropy)
         p, c = r.plan, r.cands
         info = dict(ksel=int(ksel), KP=int(c.KP), search=p.search, nprod=p.nprod, n_flagged_rows=r.n_flag,
                     # the route the search took (meld_amd.knn_plan.KnnPlan)
@@ -755,6 +759,11 @@ class HipOps:
             # the error bounds speak of the largest norm among ALL points of the search, and refine reads the query's own norm at its row
             norm2[a.q_begin : a.q_begin + a.q_count] = o.Qn[: a.q_count]
             nmax = torch.maximum(nmax, o.Qn[: a.q_count].max().reshape(1))
+        elif plan.fused_operands:
+            # queries = all the references: both layouts and the tile spheres (for _step_lists) from one read of every tile
+            o.spheres = torch.empty(lib.meld_knn16_bounds_temp_bytes(N, d, a.q_count), dtype=torch.uint8, device=dev)
+            check(lib.meld_knn16_prepare_fused(ptr(o.X_s), N, d, ptr(o.mean_s), ptr(col_min), ptr(col_max), ptr(o.Rt), ptr(o.Q), ptr(o.Qn), ptr(norm2),
+                                               ptr(nmax), ptr(o.scale_info), ptr(o.spheres), st), "meld_knn16_prepare_fused")
         elif col_min is not None:
             check(lib.meld_knn16_prepare_scaled(ptr(o.X_s), N, d, ptr(o.mean_s), ptr(col_min), ptr(col_max), *tail), "meld_knn16_prepare_scaled")
         else:
@@ -792,7 +801,8 @@ class HipOps:
             return None, None, None, None
         lib, st, dev, N, d = self.lib, _stream(), a.X.device, a.N, a.d
         X_s, mean_s, n_tiles, n_blocks = o.X_s, o.mean_s, o.n_tiles, o.q_pad // o.BQ
-        tmpb = torch.empty(lib.meld_knn16_bounds_temp_bytes(N, d, a.q_count), dtype=torch.uint8, device=dev)
+        spheres_ready = getattr(o, "spheres", None) is not None  # (meld_knn16_prepare_fused left them there)
+        tmpb = o.spheres if spheres_ready else torch.empty(lib.meld_knn16_bounds_temp_bytes(N, d, a.q_count), dtype=torch.uint8, device=dev)
         if plan.bounds == "bounds_from_spheres":
             # row-sharded build: the spheres of the reference tiles are the same on every rank (0.7 ms at 1M cells): every rank
             # computes 1 / world of them and the three arrays are all-gathered (4 MB in all)
@@ -813,14 +823,14 @@ class HipOps:
             step_list = torch.empty(n_blocks * n_tiles, dtype=torch.int32, device=dev)
             step_cnt = torch.empty(n_blocks, dtype=torch.int32, device=dev)
             scratch = torch.empty(lib.meld_knn16_list_scratch_bytes(N), dtype=torch.uint8, device=dev)
-            check(lib.meld_knn16_step_lists_direct_lead(ptr(X_s), N, d, ptr(mean_s), ptr(o.scale_info), ptr(nmax), ptr(o.Rt), ptr(seeds), ptr(o.Qn), plan.nprod,
-                                                        ptr(tmpb), ptr(scratch), ptr(step_list), n_tiles, ptr(step_cnt), int(plan.lead_bounds), st),
+            check((lib.meld_knn16_step_lists_direct_spheres if spheres_ready else lib.meld_knn16_step_lists_direct_lead)(ptr(X_s), N, d, ptr(mean_s), ptr(o.scale_info), ptr(nmax), ptr(o.Rt), ptr(seeds), ptr(o.Qn), plan.nprod,
+                ptr(tmpb), ptr(scratch), ptr(step_list), n_tiles, ptr(step_cnt), int(plan.lead_bounds), st),
                   "meld_knn16_step_lists_direct")
             del scratch
         else:
             sb = plan.seeded_bounds
             lb2 = torch.empty(lib.meld_knn16_bounds_bytes(N, a.q_count), dtype=torch.uint8, device=dev)
-            check((lib.meld_knn16_bounds_from_spheres if plan.bounds == "bounds_from_spheres" else lib.meld_knn16_bounds)(
+            check((lib.meld_knn16_bounds_from_spheres if plan.bounds == "bounds_from_spheres" or spheres_ready else lib.meld_knn16_bounds)(
                 ptr(X_s), N, d, ptr(mean_s), ptr(o.scale_info), ptr(nmax), ptr(o.Rt), a.q_begin, a.q_count, ptr(seeds) if sb else None,
                 ptr(o.Qn) if sb else None, plan.nprod, ptr(tmpb), ptr(lb2), st), "meld_knn16_bounds")
             if plan.lists == "table":
@@ -1036,10 +1046,11 @@ class HipOps:
             s.rows_at_least = int(((tot + 1) >= int(count_rows_ge)).sum())  # (+ 1: the cell itself, K_ii = 1 is carried analytically)
         return s
 
-    def _emit(self, a, r, s, ksel, assemble, symm):
+    def _emit(self, a, r, s, ksel, assemble, symm, anisotropy=None):
         """The kept entries as (keys, vals) COO pairs -- or, on a single GPU with every row local, straight into the row buckets of
         the symmetrisation (meld_coo_emit_scatter) instead of through 2 M (key, value) pairs (512 MB written and read back at 1M
-        cells).  Returns (keys, vals, assembled): assembled = (rowptr, col, val[, row sums]) of the symmetrised rows, else None."""
+        cells).  Returns (keys, vals, assembled): assembled = (rowptr, col, val[, row sums[, degrees]]) of the symmetrised rows, else
+        None; with the degrees (``anisotropy`` given), val is the kernel with the anisotropy applied."""
         lib, st, dev, q_count, n_flag_h, c = self.lib, _stream(), a.X.device, a.q_count, r.n_flag, r.cands
         M = r.m_main + s.fb_total
         assembled = None
@@ -1056,9 +1067,13 @@ class HipOps:
                                                 ptr(s.fb_off), ptr(s.fb_col), ptr(s.fb_val), s.fb_total, ptr(cursor), ptr(tcol), ptr(tval), st),
                       "meld_coo_emit_scatter")
                 a.tm.stop("coo_emit")
-                assembled = self._finish_buckets(cursor, tcol, tval, q_count, sums_diag=1.0, symm=symm)  # None: a bucket overflowed / a column thrice
+                # MELD_ASSEMBLE_FUSED_ANISO=0: the anisotropy as a pass of its own over the finished CSR (same bits)
+                aniso = anisotropy if opt("MELD_ASSEMBLE_FUSED_ANISO", "1") != "0" else None
+                assembled = self._finish_buckets(cursor, tcol, tval, q_count, sums_diag=1.0, symm=symm, anisotropy=aniso)  # None: a bucket overflowed / a column thrice
                 if assembled is not None and self.last_row_sums is not None:
                     assembled = assembled + (self.last_row_sums[1],)  # (kernel row sums incl. the unit diagonal)
+                    if self.last_degrees is not None:
+                        assembled = assembled + (self.last_degrees,)
                 a.tm.stop("symmetrize")
                 del cursor, tcol, tval
         keys = vals = None
@@ -1101,23 +1116,37 @@ class HipOps:
                                                  int(cap), ptr(counts), ptr(send), _stream()), "meld_coo_partition_remote")
         return send, counts
 
-    def _finish_buckets(self, cursor, tcol, tval, n_rows, sums_diag=None, symm=(0, 0.0)):
+    def _finish_buckets(self, cursor, tcol, tval, n_rows, sums_diag=None, symm=(0, 0.0), anisotropy=None):
         """Row buckets (meld_coo_scatter_rows / meld_coo_emit_scatter) -> CSR: every bucket sorted by column and its pairs
         of equal columns summed inside one wave, then compacted.  None when a bucket overflowed or a column occurs more
-        than twice (the caller takes the sort-based path, whose summation order is defined)."""
+        than twice (the caller takes the sort-based path, whose summation order is defined).  ``anisotropy`` (with ``sums_diag``;
+        the buckets hold ALL rows of the graph): the row sums come out of the merge, and the compaction writes
+        K_ij / (ksum_i ksum_j)^a and sums the degrees (``last_degrees``) -- the CSR is written once, with the bits of
+        ``meld_csr_compact_rows_sums`` + ``meld_csr_anisotropy_degrees``."""
         lib, st, dev = self.lib, _stream(), cursor.device
         i32 = dict(dtype=torch.int32, device=dev)
         ucnt = torch.empty(n_rows, **i32)
         flags = torch.empty(1, **i32)
-        check(lib.meld_csr_rows_sort_merge(ptr(cursor), n_rows, ptr(tcol), ptr(tval), ptr(ucnt), ptr(flags), int(symm[0]), float(symm[1]), st), "meld_csr_rows_sort_merge")
+        fused = anisotropy is not None and sums_diag is not None
+        if fused:
+            sums = torch.empty(n_rows, dtype=torch.float64, device=dev)
+            check(lib.meld_csr_rows_sort_merge_sums(ptr(cursor), n_rows, ptr(tcol), ptr(tval), ptr(ucnt), ptr(flags), int(symm[0]), float(symm[1]),
+                                                    float(sums_diag), ptr(sums), st), "meld_csr_rows_sort_merge_sums")
+        else:
+            check(lib.meld_csr_rows_sort_merge(ptr(cursor), n_rows, ptr(tcol), ptr(tval), ptr(ucnt), ptr(flags), int(symm[0]), float(symm[1]), st), "meld_csr_rows_sort_merge")
         rowptr = _scan_i32(lib, ucnt, st)
         nnz, flag = (int(v) for v in torch.stack([rowptr[n_rows], flags[0].to(torch.int64)]).tolist())  # (one read-back)
         if flag != 0:
             return None
         col = torch.empty(nnz, **i32)
         val = torch.empty(nnz, dtype=torch.float64, device=dev)
-        self.last_row_sums = None
-        if nnz > 0 and sums_diag is not None:
+        self.last_row_sums = self.last_degrees = None
+        if nnz > 0 and fused:
+            dw = torch.empty(n_rows, dtype=torch.float64, device=dev)
+            check(lib.meld_csr_compact_rows_anisotropy(ptr(rowptr), n_rows, ptr(tcol), ptr(tval), ptr(col), ptr(val), ptr(sums), float(anisotropy), ptr(dw), st),
+                  "meld_csr_compact_rows_anisotropy")
+            self.last_row_sums, self.last_degrees = (sums_diag, sums), dw
+        elif nnz > 0 and sums_diag is not None:
             # (the rows' sums on the way out of the buckets: meld_csr_row_sums' bits without its pass over the values)
             sums = torch.empty(n_rows, dtype=torch.float64, device=dev)
             check(lib.meld_csr_compact_rows_sums(ptr(rowptr), n_rows, ptr(tcol), ptr(tval), ptr(col), ptr(val), float(sums_diag), ptr(sums), st),
@@ -1638,7 +1667,7 @@ def build_knn_graph(X, knn=5, decay=40, thresh=1e-4, anisotropy=1, ksel=None, pr
     if knn_max is not None and decay is not None and math.isfinite(decay) and 36 * k1 < min(knn_max + 1, N):
         trial = ops.directed_kernel_coo(X, 0, N, knn, decay, thresh, ksel, tm=tm, force_fallback=force_fallback, assemble=True,
                                         bw_scale=bw_scale, bw_fixed=bw_fixed, col_stats=col_stats, knn_max=None, symm=symm, count_rows_ge=6 * k1,
-                                        frame_axes=frame_axes)
+                                        frame_axes=frame_axes, anisotropy=anisotropy)
         if trial[3]["rows_with_at_least"] <= N // 10 or 36 * k1 >= N / 2:
             keys, vals, bw, info = trial
             info["knn_max_uncapped_as_upstream"] = True
@@ -1647,24 +1676,26 @@ def build_knn_graph(X, knn=5, decay=40, thresh=1e-4, anisotropy=1, ksel=None, pr
     if info is None:
         keys, vals, bw, info = ops.directed_kernel_coo(X, 0, N, knn, decay, thresh, ksel, tm=tm, force_fallback=force_fallback, assemble=True,
                                                        bw_scale=bw_scale, bw_fixed=bw_fixed, col_stats=col_stats, knn_max=knn_max, symm=symm,
-                                                       frame_axes=frame_axes)
+                                                       frame_axes=frame_axes, anisotropy=anisotropy)
     if bw_scale != 1.0:  # (the stages record the unscaled bandwidth; the graph reports the one the kernel used)
         bw = (bw * bw_scale).clamp_(min=float(np.finfo(float).eps))
     if info.get("nnz_directed", 0) == 0:
         raise ValueError("the kernel has no off-diagonal entries; cannot build a graph")
     tm.start()
-    ksum = None
+    ksum = dw = None
     if info.get("assembled") is not None:  # (the kept candidates went straight into the row buckets)
         asm = info.pop("assembled")
         rowptr, col, val = asm[:3]
         ksum = asm[3] if len(asm) > 3 else None  # (the row sums came out of the buckets with the rows)
+        dw = asm[4] if len(asm) > 4 else None  # (... and the anisotropy was applied, the degrees summed, on the way out)
     else:
         rowptr, col, val = ops.assemble_rows(keys, vals, 0, N, N, symm=symm)
     del keys, vals
     tm.stop("symmetrize")
     if ksum is None:
         ksum = ops.row_sums(rowptr, val, N, 1.0)
-    dw = ops.anisotropy_degrees(rowptr, col, val, N, ksum, 0, anisotropy)
+    if dw is None:
+        dw = ops.anisotropy_degrees(rowptr, col, val, N, ksum, 0, anisotropy)
     tm.stop("anisotropy_degree")
 
     nnz = int(col.shape[0])

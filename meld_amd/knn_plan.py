@@ -74,6 +74,10 @@ class KnnPlan:
     # the direct step lists take their bounds from K block 0 alone (None: as the route implies, i.e. direct lists in the frame)
     lead_bounds: Optional[bool] = None
     partial_forced: bool = False  # partial_in_search set by MELD_KNN16_EE, not by the frame: without_frame() keeps it
+    # queries = all the references, pruned: Rt, Q and the tile spheres from ONE pass over the cells (meld_knn16_prepare_fused)
+    # (how the operands are written, not which route the search takes: same bits either way, so two plans that differ in this alone
+    # compare equal)
+    fused_operands: bool = dataclasses.field(default=False, compare=False)
 
     def __post_init__(self):
         if self.lead_bounds is None:
@@ -154,5 +158,8 @@ def plan_knn_search(lib, N, d, q_begin, q_count, knn, ksel, *, options, cross=Fa
     # the direct lists in the frame take their bounds from K block 0 alone (lower bounds all the same, for a quarter of the tile
     # stream); MELD_KNN16_LEAD_BOUNDS=0: from all K blocks
     lead_bounds = lists == "direct" and frame and opt("MELD_KNN16_LEAD_BOUNDS", "1") != "0"
+    # One pass over the cells for both operand layouts and the tile spheres where the queries are all the references and the
+    # spheres are wanted here (pruned, not shared between ranks).  MELD_KNN_FUSED_OPERANDS=0: the three separate passes (same bits).
+    fused = prune and bounds != "bounds_from_spheres" and q_begin == 0 and q_count == N and opt("MELD_KNN_FUSED_OPERANDS", "1") != "0"
     return KnnPlan(search, nprod, frame, radius_cut, prune, seed, 0 if seed == "bandwidth" else knn, bounds, seeded_bounds, lists,
-                   block_order, main_slices, two_pass, partial, nprod == 1, lead_bounds, ee is not None)
+                   block_order, main_slices, two_pass, partial, nprod == 1, lead_bounds, ee is not None, fused)
