@@ -15,14 +15,13 @@ Host code here only evaluates the M+1 scalar coefficients and sequences kernel l
 """
 from __future__ import annotations
 
-from ._options import is_set, opt
-
-import os
+from ._options import opt
 
 import numpy as np
 import torch
 
 from ._lib import check, get_lib, ptr
+from .graph import HipOps, _EventSpan
 
 __all__ = ["filter", "filter_sweep", "chebyshev_coefficients", "spectral_kernel", "lanczos_lmax", "chebyshev_apply", "IndicatorSignal"]
 
@@ -48,13 +47,16 @@ class IndicatorSignal:
         out[np.arange(self.shape[0]), codes] = 1.0 if self.scale is None else self.scale[codes]
         return out
 
+    def _codes_on(self, device):
+        """The codes as an int64 tensor on ``device`` (host codes cross PCIe as int32)."""
+        if isinstance(self.codes, torch.Tensor):
+            return self.codes.to(device=device, dtype=torch.int64)
+        return torch.from_numpy(self.codes.astype(np.int32)).to(device).to(torch.int64)
+
     def to_device_ordered(self, device, perm, n_pad):
         """The [n_pad, p] signal on the device with row i = the indicator row of cell perm[i] (perm None: i) and zero rows
         behind the N cells: ``meld_indicator_signal``, one pass instead of zeros / gather / scatter / index_select / cat."""
-        if isinstance(self.codes, torch.Tensor):
-            codes = self.codes.to(device=device, dtype=torch.int64)
-        else:
-            codes = torch.from_numpy(self.codes.astype(np.int32)).to(device).to(torch.int64)
+        codes = self._codes_on(device)
         scale = None if self.scale is None else torch.from_numpy(self.scale).to(device)
         out = torch.empty((int(n_pad), self.n_columns), dtype=torch.float64, device=device)
         check(get_lib().meld_indicator_signal(ptr(codes.contiguous()), ptr(scale), ptr(perm), self.shape[0], int(n_pad), self.n_columns,
@@ -62,10 +64,7 @@ class IndicatorSignal:
         return out
 
     def to_device(self, device):
-        if isinstance(self.codes, torch.Tensor):
-            codes = self.codes.to(device=device, dtype=torch.int64)
-        else:
-            codes = torch.from_numpy(self.codes.astype(np.int32)).to(device).to(torch.int64)
+        codes = self._codes_on(device)
         out = torch.zeros(self.shape, dtype=torch.float64, device=device)
         if self.scale is None:
             vals = torch.ones(self.shape[0], dtype=torch.float64, device=device)
@@ -79,16 +78,14 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
-_PINNED = {}  # (shape, dtype) -> pinned host staging buffer of the last result copied back
-
-
 class _PinnedPool:
     """Pinned result buffers handed to the caller WITHOUT a host copy.  The densities leave the device through pinned memory
     (pageable copies run at a few GB/s) and used to be copied once more into a fresh array because the staging buffer is
     reused by the next call (0.4 ms for 16 MB).  Now the caller's array IS the pinned buffer: a finalizer on that array --
     which fires when the array and every view of it (the DataFrame's) are gone -- returns the buffer to the pool.  At most
     ``MAX_OUT`` buffers of a shape are lent out at a time (pinning a new one costs milliseconds and pinned memory is a
-    shared resource); beyond that the result is copied as before."""
+    shared resource); beyond that, and with ``MELD_PINNED_RESULT=0``, the result goes through the one staging buffer the pool
+    keeps for that and is copied out of it."""
 
     MAX_OUT = 4
     MAX_FREE_BYTES = 256 << 20  # page-locked memory parked in the pool (not lent out) at most
@@ -96,6 +93,7 @@ class _PinnedPool:
     def __init__(self):
         self.free = {}  # key -> [tensor, ...]
         self.out = {}   # key -> number lent out
+        self.staging = {}  # key -> the staging buffer of the copy path (one entry: a new graph per fit would pin 16 MB each time)
         self.last_path = None  # "pinned" / "copy": which way the last result went (observable: tests, diagnostics)
 
     def _free_bytes(self):
@@ -113,21 +111,28 @@ class _PinnedPool:
         while len(lst) > 1 and self._free_bytes() > self.MAX_FREE_BYTES:
             lst.pop()
 
-    def lend(self, r):
-        """r: device tensor -> numpy array with its values (device synchronised), or None when the pool is exhausted."""
+    def to_host(self, r, lend=True):
+        """r: device tensor -> numpy array with its values (device synchronised): a pinned buffer lent to the caller, or a
+        copy out of the staging buffer when ``lend`` is false or the pool is exhausted."""
         import weakref
 
         key = (tuple(r.shape), r.dtype)
         free = self.free.setdefault(key, [])
-        if not free and self.out.get(key, 0) >= self.MAX_OUT:
-            self.last_path = "copy"
-            return None
-        if not free:
-            self._evict(key)  # (about to pin a new buffer: make room first)
-        self.last_path = "pinned"
-        stage = free.pop() if free else torch.empty(r.shape, dtype=r.dtype, pin_memory=True)
+        copy = not lend or (not free and self.out.get(key, 0) >= self.MAX_OUT)
+        self.last_path = "copy" if copy else "pinned"
+        if copy:
+            if key not in self.staging:
+                self.staging.clear()
+                self.staging[key] = torch.empty(r.shape, dtype=r.dtype, pin_memory=True)
+            stage = self.staging[key]
+        else:
+            if not free:
+                self._evict(key)  # (about to pin a new buffer: make room first)
+            stage = free.pop() if free else torch.empty(r.shape, dtype=r.dtype, pin_memory=True)
         stage.copy_(r, non_blocking=True)
         torch.cuda.current_stream().synchronize()
+        if copy:
+            return stage.numpy().copy()
         arr = stage.numpy()
         self.out[key] = self.out.get(key, 0) + 1
 
@@ -171,8 +176,6 @@ def chebyshev_coefficients(h, lmax, m):
 def _ops_of(G):
     ops = getattr(G, "ops", None)
     if ops is None:
-        from .graph import HipOps
-
         ops = HipOps(G.val.device)
         G.ops = ops
     return ops
@@ -209,8 +212,6 @@ def chebyshev_apply(G, signal, coeffs, lmax):
     t_cur = torch.zeros_like(t_old)
     r = torch.empty_like(_local(G, t_old))
     ops.scale(_local(G, t_old), 0.5 * c[0], r)
-    from .graph import _EventSpan
-
     ops.cheby_step(G, p, t_old, G.row_begin, None, _local(G, t_cur), r, 1.0 / a1, -a2 / a1, 0.0, c[1])
     if comm is not None:
         comm.all_gather_rows(t_cur, _local(G, t_cur))
@@ -283,6 +284,23 @@ def _ritz_check(alphas, betas, tol):
     return theta, resid
 
 
+def _first_converged(alphas, betas, lo, hi, check_every, max_iter, tol):
+    """The stopping rule of the Lanczos drivers over the prefixes k in (lo, hi] of the tridiagonal entries (the arrays may be
+    longer than hi).  A prefix is examined when k is a multiple of ``check_every``, at ``max_iter`` and at a breakdown
+    (beta_k negligible against alpha_k, or not finite); the rule fires at a breakdown or when the relative Ritz residual is
+    <= tol.  Returns (k, theta, resid, stopped): the first prefix at which it fires, or hi with the last (theta, resid)
+    examined ((0, inf) when none was) and ``stopped`` false.  However the prefixes are cut into calls, the first
+    ``stopped`` comes at the same k with the same values."""
+    theta, resid = 0.0, float("inf")
+    for k in range(lo + 1, hi + 1):
+        done = betas[k - 1] <= 1e-14 * max(abs(alphas[k - 1]), 1e-300) or not np.isfinite(betas[k - 1])
+        if k % check_every == 0 or done or k == max_iter:
+            theta, resid = _ritz_check(alphas[:k], betas[:k], tol)
+            if resid <= tol or done:
+                return k, theta, resid, True
+    return hi, theta, resid, False
+
+
 class _LanczosHostSide:
     """What the host's half of the device-resident Lanczos loop keeps per device: a side stream that carries the tridiagonal
     entries to a pinned buffer behind every batch of iterations, so that the main stream never waits for a convergence check."""
@@ -335,12 +353,6 @@ def _lanczos_lmax_device(G, ops, u0, tol, max_iter, check_every):
     stop = torch.zeros(1, dtype=torch.int32, device=dev)  # set once the check has passed: what is left of the batch in flight is void
     stop.record_stream(host.side)
 
-    def finish(theta, info):
-        if in_flight > 1:
-            with torch.cuda.stream(host.side):
-                stop.fill_(1)
-        return theta, info
-
     def enqueue(lo, hi):
         """iterations [lo, hi) on the main stream, their alphas / betas to the pinned buffer behind them on the side stream"""
         ops.lanczos_steps(G, V, state, alphas_d, betas_d, lo, hi - lo, scratch, stop)
@@ -356,24 +368,19 @@ def _lanczos_lmax_device(G, ops, u0, tol, max_iter, check_every):
 
     it = min(4 * check_every, max_iter)
     pending = [enqueue(0, it)]
-    theta, resid, examined = 0.0, float("inf"), 0
-    while pending or it < max_iter:
+    k, theta, resid, stopped = 0, 0.0, float("inf"), False
+    while not stopped and (pending or it < max_iter):
         while it < max_iter and len(pending) < in_flight:
             hi = min(it + check_every, max_iter)
             pending.append(enqueue(it, hi))
             it = hi
         lo, hi, landed = pending.pop(0)
         landed.synchronize()
-        alphas, betas = host.ab[0, :hi].numpy(), host.ab[1, :hi].numpy()
-        # examine the prefixes a per-iteration loop would have examined
-        for k in range(lo + 1, hi + 1):
-            done = betas[k - 1] <= 1e-14 * max(abs(alphas[k - 1]), 1e-300) or not np.isfinite(betas[k - 1])
-            if k % check_every == 0 or done or k == max_iter:
-                theta, resid = _ritz_check(alphas[:k], betas[:k], tol)
-                if resid <= tol or done:
-                    return finish(theta, dict(iterations=k, residual=resid, tol=tol, device_resident=True, enqueued=it))
-        examined = hi
-    return theta, dict(iterations=examined, residual=resid, tol=tol, device_resident=True, enqueued=it)
+        k, theta, resid, stopped = _first_converged(host.ab[0, :hi].numpy(), host.ab[1, :hi].numpy(), lo, hi, check_every, max_iter, tol)
+    if stopped and in_flight > 1:
+        with torch.cuda.stream(host.side):
+            stop.fill_(1)
+    return theta, dict(iterations=k, residual=resid, tol=tol, device_resident=True, enqueued=it)
 
 
 def _lanczos_lmax_phases(G, ops, comm, u0, tol, max_iter, check_every):
@@ -394,34 +401,28 @@ def _lanczos_lmax_phases(G, ops, comm, u0, tol, max_iter, check_every):
     betas_d = torch.zeros(max_iter, dtype=torch.float64, device=dev)
     dots = torch.zeros(2 * slots, dtype=torch.float64, device=dev)
     nrm2 = torch.zeros(slots, dtype=torch.float64, device=dev)
-    it, theta, resid = 0, 0.0, float("inf")
+    it, k, theta, resid, stopped = 0, 0, 0.0, float("inf"), False
     batch = 4 * check_every
-    while it < max_iter:
+    while it < max_iter and not stopped:
         n_iter = min(batch, max_iter - it)
-        for k in range(it, it + n_iter):
-            u_prev, u, y = V[k % 3], V[(k + 1) % 3], V[(k + 2) % 3]
+        for i in range(it, it + n_iter):
+            u_prev, u, y = V[i % 3], V[(i + 1) % 3], V[(i + 2) % 3]
             ops.lanczos_spmv(G, u, _local(G, u_prev), _local(G, y), state, dots)
             if comm is not None:
                 comm.all_reduce_sum(dots)
-            ops.lanczos_alpha(state, dots, nrm2, alphas_d, k)
+            ops.lanczos_alpha(state, dots, nrm2, alphas_d, i)
             ops.lanczos_axpy(_local(G, u), _local(G, y), state, nrm2)
             if comm is not None:
                 comm.all_reduce_sum(nrm2)
-            ops.lanczos_beta(state, nrm2, dots, betas_d, k)
+            ops.lanczos_beta(state, nrm2, dots, betas_d, i)
             if comm is not None:
                 comm.all_gather_rows(y, _local(G, y))
         it_new = it + n_iter
         ab = torch.stack([alphas_d[:it_new], betas_d[:it_new]]).cpu().numpy()  # the one synchronisation per batch
-        alphas, betas = ab[0], ab[1]
-        for k in range(it + 1, it_new + 1):
-            done = betas[k - 1] <= 1e-14 * max(abs(alphas[k - 1]), 1e-300) or not np.isfinite(betas[k - 1])
-            if k % check_every == 0 or done or k == max_iter:
-                theta, resid = _ritz_check(alphas[:k], betas[:k], tol)
-                if resid <= tol or done:
-                    return theta, dict(iterations=k, residual=resid, tol=tol, device_resident=True)
+        k, theta, resid, stopped = _first_converged(ab[0], ab[1], it, it_new, check_every, max_iter, tol)
         it = it_new
         batch = check_every
-    return theta, dict(iterations=it, residual=resid, tol=tol, device_resident=True)
+    return theta, dict(iterations=k, residual=resid, tol=tol, device_resident=True)
 
 
 def _lanczos_lmax_folded(G, ops, comm, u0, tol, max_iter, check_every):
@@ -443,10 +444,10 @@ def _lanczos_lmax_folded(G, ops, comm, u0, tol, max_iter, check_every):
     nrm2 = acc[2 * slots :]
     u_loc0 = _local(G, V[1])
     nrm2[0] = torch.dot(u_loc0, u_loc0)
-    it, theta, resid = 0, 0.0, float("inf")  # it = iterations run; prefixes 1 .. it - 1 have their beta
+    it, theta, resid, stopped = 0, 0.0, float("inf"), False  # it = iterations run; prefixes 1 .. it - 1 have their beta
     examined = 0
     target = min(4 * check_every, max_iter)
-    while examined < max_iter:
+    while examined < max_iter and not stopped:
         n_batch = min(target + 1, max_iter + 1) - it
         if comm is not None and n_batch > 0 and hasattr(ops, "lanczos_steps_sharded") \
                 and ops.lanczos_steps_sharded(G, V, state, acc, alphas_d, betas_d, it, n_batch):
@@ -463,14 +464,8 @@ def _lanczos_lmax_folded(G, ops, comm, u0, tol, max_iter, check_every):
                 comm.all_gather_rows(y, _local(G, y))
             it += 1
         ab = torch.stack([alphas_d[:it], betas_d[:it]]).cpu().numpy()  # the one synchronisation per batch
-        alphas, betas = ab[0], ab[1]
-        for k in range(examined + 1, it):  # beta_k = betas[k - 1] was written by iteration k (0-based), i.e. k + 1 <= it
-            done = betas[k - 1] <= 1e-14 * max(abs(alphas[k - 1]), 1e-300) or not np.isfinite(betas[k - 1])
-            if k % check_every == 0 or done or k == max_iter:
-                theta, resid = _ritz_check(alphas[:k], betas[:k], tol)
-                if resid <= tol or done:
-                    return theta, dict(iterations=k, residual=resid, tol=tol, device_resident=True, all_reduces_per_iteration=1)
-        examined = it - 1
+        # beta_k = betas[k - 1] was written by iteration k (0-based), i.e. k + 1 <= it
+        examined, theta, resid, stopped = _first_converged(ab[0], ab[1], examined, it - 1, check_every, max_iter, tol)
         target = min(examined + check_every, max_iter)
     return theta, dict(iterations=examined, residual=resid, tol=tol, device_resident=True, all_reduces_per_iteration=1)
 
@@ -478,20 +473,18 @@ def _lanczos_lmax_folded(G, ops, comm, u0, tol, max_iter, check_every):
 def lanczos_lmax(G, tol=3e-4, max_iter=300, check_every=5, seed=0):
     """Largest eigenvalue of L = diag(dw) - W by the Lanczos recurrence on the device SpMV.
 
-    Vectors stay un-normalised on the device (u_k = beta_{k-1} v_k); the 1/beta scalings are folded
-    into the alpha/gamma arguments of ``meld_cheby_step``, which also returns <y, u>, so one
-    iteration = one SpMV kernel + one axpby kernel (which returns |w|^2 directly -- the shortcut
-    |y|^2 - alpha^2 is unstable) + two small read-backs (+ two scalar all-reduces and one
-    all-gather of the new vector on a sharded graph).  Convergence: relative Ritz residual
-    |beta_m s_m| / theta <= tol (s = last component of the top eigenvector of the tridiagonal
-    matrix); the eigenvalue error is then ~ tol^2 / gap, far below tol (measured < 1e-8 relative
-    at tol = 1e-4, against the 1e-4..1e-5 run-to-run spread of the reference's own estimate)."""
+    Every scalar of the recurrence stays on the device; the host enqueues batches of iterations, reads the tridiagonal
+    entries back once per batch and applies the one stopping rule (``_first_converged``).  Three drivers, chosen by what
+    ``ops`` offers: ``_lanczos_lmax_device`` on a single GPU (``meld_lanczos_steps``, the checks overlapped with the next
+    batch), and on a row-sharded graph ``_lanczos_lmax_folded`` (one all-reduce and one all-gather of the new vector per
+    iteration) or, with ``MELD_LANCZOS_FOLD=0``, ``_lanczos_lmax_phases`` (two all-reduces).  Convergence: relative Ritz
+    residual |beta_m s_m| / theta <= tol (s = last component of the top eigenvector of the tridiagonal matrix); the
+    eigenvalue error is then ~ tol^2 / gap, far below tol (measured < 1e-8 relative at tol = 1e-4, against the 1e-4..1e-5
+    run-to-run spread of the reference's own estimate)."""
     ops = _ops_of(G)
     comm = getattr(G, "comm", None)
-    dev = G.val.device
-    slots = ops.dot_slots()
     # deterministic start vector, generated where it is used (a 1M-entry CPU randn costs 15 ms)
-    idx = torch.arange(G.n_pad, dtype=torch.float64, device=dev)
+    idx = torch.arange(G.n_pad, dtype=torch.float64, device=G.val.device)
     u = torch.frac(torch.sin(idx * 12.9898 + float(seed) + 1.0) * 43758.5453) - 0.5
     u[G.N :] = 0.0
     max_iter = min(max_iter, G.N)
@@ -501,46 +494,63 @@ def lanczos_lmax(G, tol=3e-4, max_iter=300, check_every=5, seed=0):
         return _lanczos_lmax_folded(G, ops, comm, u, tol, max_iter, check_every)
     if hasattr(ops, "lanczos_spmv"):
         return _lanczos_lmax_phases(G, ops, comm, u, tol, max_iter, check_every)
-    nrm = float(torch.linalg.vector_norm(u).item())
-    u_prev = torch.zeros(G.n_pad, dtype=torch.float64, device=dev)
-    y = torch.zeros(G.n_pad, dtype=torch.float64, device=dev)
-    dots = torch.zeros(2 * slots, dtype=torch.float64, device=dev)
-    nrm2 = torch.zeros(slots, dtype=torch.float64, device=dev)
+    raise TypeError("{} has none of lanczos_steps, lanczos_fold, lanczos_spmv: no Lanczos driver can run on it".format(type(ops).__name__))
 
-    def total(t):
-        s = t.sum().reshape(1)
-        if comm is not None:
-            comm.all_reduce_sum(s)
-        return float(s.item())
 
-    alphas, betas = [], []
-    s_cur = 1.0 / nrm  # v_k = s_cur * u
-    s_prev = 0.0
-    beta_prev = 0.0
-    theta, resid = 0.0, float("inf")
-    it = 0
-    max_iter = min(max_iter, G.N)
-    while it < max_iter:
-        # y = L v_k - beta_{k-1} v_{k-1}   (local rows)
-        ops.cheby_step(G, 1, u, G.row_begin, _local(G, u_prev), _local(G, y), None, s_cur, 0.0, -beta_prev * s_prev, 0.0, dots)
-        alpha = total(dots[:slots]) * s_cur  # <y, v_k>
-        # w = y - alpha v_k (stored in y), beta = |w|
-        ops.axpby(-alpha * s_cur, _local(G, u), 1.0, _local(G, y), nrm2)
-        beta = float(np.sqrt(total(nrm2)))
-        alphas.append(alpha)
-        it += 1
-        done = beta <= 1e-14 * max(abs(alpha), 1e-300)
-        if it % check_every == 0 or done or it == max_iter:
-            theta, resid = _ritz_check(alphas, betas + [beta], tol)  # (the tridiagonal solver: see there for why not a dense eigh)
-            if resid <= tol or done:
-                break
-        if comm is not None:
-            comm.all_gather_rows(y, _local(G, y))
-        betas.append(beta)
-        u_prev, u, y = u, y, u_prev
-        s_prev, s_cur = s_cur, 1.0 / beta
-        beta_prev = beta
-    return theta, dict(iterations=it, residual=resid, tol=tol)
+def _checked_signal(signal, graph):
+    """``signal`` as an ``IndicatorSignal`` or an fp64 ndarray [N, p], or the ValueError of the reference."""
+    if isinstance(signal, IndicatorSignal):
+        sig = signal
+    else:
+        sig = np.asarray(getattr(signal, "values", signal), dtype=np.float64)
+    if sig.shape[0] != graph.N:
+        raise ValueError("First dimension should be the number of nodes G.N = {}, got {}.".format(graph.N, sig.shape))
+    if not isinstance(sig, IndicatorSignal):
+        if sig.ndim == 1:
+            sig = sig[:, None]
+        if sig.ndim != 2:
+            raise ValueError("At most 2 dimensions are supported.")
+    return sig
+
+
+def _to_device_order(signal, graph):
+    """A checked signal as the [n_pad, p] fp64 tensor the recurrence reads: on the graph's device, in its row order, zero
+    rows behind the N cells."""
+    dev = graph.val.device
+    perm = getattr(graph, "perm", None)
+    if isinstance(signal, IndicatorSignal):
+        if dev.type == "cuda":
+            # the scaled one-hot straight in the device's row order, padding rows included (meld_indicator_signal: one pass)
+            return signal.to_device_ordered(dev, perm, graph.n_pad)
+        s_dev = signal.to_device(dev)
+    else:
+        s_dev = torch.from_numpy(np.ascontiguousarray(signal)).to(dev)
+    if perm is not None:  # device arrays live in the locality order
+        s_dev = s_dev.index_select(0, perm)
+    if graph.n_pad != graph.N:  # sharded graph: isolated padding rows at the end
+        s_dev = torch.cat([s_dev, torch.zeros(graph.n_pad - graph.N, s_dev.shape[1], dtype=s_dev.dtype, device=dev)])
+    return s_dev
+
+
+def _to_caller_order(r, graph):
+    """The local rows [..., rows_pad, p] of a result as [..., N, p] in the caller's row order: all-gather on a shard, cut to
+    the N cells, inverse permutation."""
+    comm = getattr(graph, "comm", None)
+    if comm is not None:
+        full = torch.empty(r.shape[:-2] + (graph.n_pad, r.shape[-1]), dtype=r.dtype, device=r.device)
+        for full_b, r_b in zip(full.view(-1, *full.shape[-2:]), r.reshape(-1, *r.shape[-2:])):
+            comm.all_gather_rows(full_b, r_b.contiguous())
+        r = full
+    r = r[..., : graph.N, :]
+    perm = getattr(graph, "perm", None)
+    if perm is not None:
+        r_orig = torch.empty_like(r)
+        if r.dim() == 2 and r.is_cuda and r.dtype == torch.float64 and r.is_contiguous():
+            check(get_lib().meld_scatter_rows_f64(ptr(r), ptr(perm), int(r.shape[0]), int(r.shape[1]), ptr(r_orig), _stream()), "meld_scatter_rows_f64")
+        else:
+            r_orig[..., perm, :] = r
+        r = r_orig
+    return r
 
 
 def filter_sweep(signal, graph, filter, betas, offset=0, order=1, chebyshev_order=None):  # noqa: A002
@@ -554,32 +564,9 @@ def filter_sweep(signal, graph, filter, betas, offset=0, order=1, chebyshev_orde
     if chebyshev_order is None:
         chebyshev_order = 30
     C = np.stack([chebyshev_coefficients(spectral_kernel(filter, b, offset, order, graph.lmax), graph.lmax, chebyshev_order) for b in betas])
-    is_ind = isinstance(signal, IndicatorSignal)
-    sig = signal if is_ind else np.asarray(getattr(signal, "values", signal), dtype=np.float64)
-    if sig.shape[0] != graph.N:
-        raise ValueError("First dimension should be the number of nodes G.N = {}, got {}.".format(graph.N, sig.shape))
-    if not is_ind and sig.ndim == 1:
-        sig = sig[:, None]
-    dev = graph.val.device
-    s_dev = sig.to_device(dev) if is_ind else torch.from_numpy(np.ascontiguousarray(sig)).to(dev)
-    perm = getattr(graph, "perm", None)
-    if perm is not None:
-        s_dev = s_dev.index_select(0, perm)
-    if graph.n_pad != graph.N:
-        s_dev = torch.cat([s_dev, torch.zeros(graph.n_pad - graph.N, s_dev.shape[1], dtype=s_dev.dtype, device=dev)])
+    s_dev = _to_device_order(_checked_signal(signal, graph), graph)
     R = chebyshev_apply(graph, s_dev, C, graph.lmax)  # [B, rows_pad, p]
-    comm = getattr(graph, "comm", None)
-    if comm is not None:
-        full = torch.empty(R.shape[0], graph.n_pad, R.shape[2], dtype=R.dtype, device=dev)
-        for b in range(R.shape[0]):
-            comm.all_gather_rows(full[b], R[b].contiguous())
-        R = full
-    R = R[:, : graph.N]
-    if perm is not None:
-        out = torch.empty_like(R)
-        out[:, perm] = R
-        R = out
-    return R.cpu().numpy()
+    return _to_caller_order(R, graph).cpu().numpy()
 
 
 def filter(signal, graph, filter, beta, offset=0, order=1, solver="chebyshev", chebyshev_order=None):  # noqa: A001,A002
@@ -588,65 +575,22 @@ def filter(signal, graph, filter, beta, offset=0, order=1, solver="chebyshev", c
     an ``ndarray`` squeezed like pygsp's ``Filter.filter`` output."""
     graph.estimate_lmax()
     h = spectral_kernel(filter, beta, offset, order, graph.lmax)  # raises NotImplementedError
-
-    is_ind = isinstance(signal, IndicatorSignal)
-    sig = signal if is_ind else np.asarray(getattr(signal, "values", signal), dtype=np.float64)
-    if sig.shape[0] != graph.N:
-        raise ValueError("First dimension should be the number of nodes G.N = {}, got {}.".format(graph.N, sig.shape))
-    if not is_ind:
-        if sig.ndim == 1:
-            sig = sig[:, None]
-        if sig.ndim != 2:
-            raise ValueError("At most 2 dimensions are supported.")
-    dev = graph.val.device
+    sig = _checked_signal(signal, graph)
 
     if solver == "chebyshev":
         if chebyshev_order is None:
             chebyshev_order = 30  # pygsp's default order
         c = chebyshev_coefficients(h, graph.lmax, chebyshev_order)
-        perm = getattr(graph, "perm", None)
-        if is_ind and dev.type == "cuda":
-            # the scaled one-hot straight in the device's row order, padding rows included (meld_indicator_signal: one pass)
-            s_dev = sig.to_device_ordered(dev, perm, graph.n_pad)
-        else:
-            s_dev = sig.to_device(dev) if is_ind else torch.from_numpy(np.ascontiguousarray(sig)).to(dev)
-            if perm is not None:  # device arrays live in the locality order
-                s_dev = s_dev.index_select(0, perm)
-            if graph.n_pad != graph.N:  # sharded graph: isolated padding rows at the end
-                s_dev = torch.cat([s_dev, torch.zeros(graph.n_pad - graph.N, s_dev.shape[1], dtype=s_dev.dtype, device=dev)])
-        r = chebyshev_apply(graph, s_dev, c, graph.lmax)
-        comm = getattr(graph, "comm", None)
-        if comm is not None:
-            r_full = torch.empty_like(s_dev)
-            comm.all_gather_rows(r_full, r)
-            r = r_full
-        r = r[: graph.N]
-        if perm is not None:
-            r_orig = torch.empty_like(r)
-            if r.is_cuda and r.dtype == torch.float64 and r.is_contiguous():
-                check(get_lib().meld_scatter_rows_f64(ptr(r), ptr(perm), int(r.shape[0]), int(r.shape[1]), ptr(r_orig), _stream()), "meld_scatter_rows_f64")
-            else:
-                r_orig[perm] = r
-            r = r_orig
-        # D2H through a pinned staging buffer kept on the graph (pageable copies run at a few GB/s)
-        out = _POOL.lend(r) if (r.is_cuda and opt("MELD_PINNED_RESULT", "1") != "0") else None
-        if out is not None:
-            pass
-        elif r.is_cuda:
-            stage = _PINNED.get((tuple(r.shape), r.dtype))  # (process-wide: a new graph per fit would pin 16 MB each time)
-            if stage is None:
-                _PINNED.clear()
-                stage = torch.empty(r.shape, dtype=r.dtype, pin_memory=True)
-                _PINNED[(tuple(r.shape), r.dtype)] = stage
-            stage.copy_(r, non_blocking=True)
-            torch.cuda.current_stream().synchronize()
-            out = stage.numpy().copy()
+        r = _to_caller_order(chebyshev_apply(graph, _to_device_order(sig, graph), c, graph.lmax), graph)
+        if r.is_cuda:
+            # D2H through pinned memory (pageable copies run at a few GB/s), lent to the caller where the pool allows
+            out = _POOL.to_host(r, lend=opt("MELD_PINNED_RESULT", "1") != "0")
         else:  # CPU tensors only occur in the gloo tests of the sharded driver
             out = r.numpy().copy()
     elif solver == "exact":
         from .dense import exact_filter
 
-        out = exact_filter(graph, sig.to_dense() if is_ind else sig,
+        out = exact_filter(graph, sig.to_dense() if isinstance(sig, IndicatorSignal) else sig,
                            lambda lm: spectral_kernel(filter, beta, offset, order, lm))
     else:
         raise ValueError("Unknown method {}.".format(solver))

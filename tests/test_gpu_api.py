@@ -611,6 +611,43 @@ def test_beta_sweep_in_one_pass_equals_separate_transforms():
         np.testing.assert_allclose(R[b], mfilter.filter(s, op.graph, "laplacian", beta, order=2, chebyshev_order=25), rtol=0, atol=1e-13)
 
 
+@pytest.mark.parametrize("n", [5003, 9001])  # below the 8192 cells from which the build reorders them: the test's own permutation / the build's
+@pytest.mark.parametrize("kind", ["dense", "indicator"])
+def test_sweep_of_one_beta_equals_the_single_filter(kind, n):
+    """``filter_sweep`` and ``filter`` bring a signal into the device's row order and the result back through the same two
+    functions, for a dense signal and for label codes alike; with a permutation in play and a common lmax, the sweep of
+    one beta is the single filter.  Not bit for bit, and not at the commit before the shared staging either: the batch
+    path accumulates with ``addcmul_``, the single path inside the kernel (measured at 5003 cells: 1.1e-19 at beta 1 and
+    8.1e-20 at beta 60 against densities of 4.0e-4 and 2.0e-4, the same figures before and after).  The bound is the one
+    of ``test_beta_sweep_in_one_pass_equals_separate_transforms``: 1e-13 of the largest density."""
+    import torch
+
+    meld = _meld()
+    from meld_amd import filter as mfilter
+
+    rng = np.random.default_rng(21)
+    X = rng.normal(size=(n, 6))
+    if n < 8192:  # the graph of the permuted cells with the permutation attached is what the build makes of larger inputs
+        perm = rng.permutation(n)
+        G = meld.MELD(knn=7, verbose=0).fit(X[perm]).graph
+        assert G.perm is None
+        G.perm = torch.from_numpy(perm).to(G.val.device)
+    else:
+        G = meld.MELD(knn=7, verbose=0).fit(X).graph
+    assert G.perm is not None
+    G.lmax = G.estimate_lmax()  # (pinned: both calls see this value)
+    codes = rng.integers(0, 2, size=n)
+    s = mfilter.IndicatorSignal(codes, 2, 1.0 / np.bincount(codes, minlength=2))
+    if kind == "dense":
+        s = s.to_dense()
+    for beta in (1.0, 60.0):
+        one = mfilter.filter(s, G, "heat", beta)
+        swept = mfilter.filter_sweep(s, G, "heat", [beta])[0]
+        assert swept.shape == one.shape == (n, 2)
+        print("{} signal, {} cells, beta {}: max |sweep - single| = {:.3e}, max |single| = {:.3e}".format(kind, n, beta, np.abs(swept - one).max(), np.abs(one).max()))
+        np.testing.assert_allclose(swept, one, rtol=0, atol=1e-13 * np.abs(one).max())
+
+
 def _two_batches(n_per=400, d=6, seed=0, shift=0.4):
     rng = np.random.default_rng(seed)
     a = rng.normal(size=(n_per, d))
