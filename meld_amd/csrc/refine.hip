@@ -563,7 +563,22 @@ extern "C" int meld_knn_radius_exact(const double* X, int64_t N, int d, int64_t 
   MELD_CHECK_ARG(X && flag_rows && bw && n_flag > 0 && N > 0 && d > 0, "meld_knn_radius_exact: bad arguments");
   MELD_CHECK_ARG(mode == 0 ? (fb_cnt && err_flag && fb_cursor) : (fb_off && fb_cursor && fb_col && fb_val),
                  "meld_knn_radius_exact: missing output for mode %d", mode);
-  const size_t lds = sizeof(double) * RB_FALL * d;
+  const size_t lds = sizeof(double) * RB_FALL * (size_t)d;
+  // the query rows of a workgroup sit in dynamic LDS: beyond the 64 KB a launch gets without asking (d > 1023) the kernel's limit
+  // is raised, once per device, to what a gfx950 workgroup can hold (160 KB less the kernel's static counters: d <= 2559)
+  constexpr size_t lds_default = 64 * 1024 - 2 * RB_FALL * sizeof(int), lds_max = 160 * 1024 - 2 * RB_FALL * sizeof(int);
+  MELD_CHECK_ARG(lds <= lds_max, "meld_knn_radius_exact: d=%d needs %zu bytes of LDS for the %d rows of a workgroup, more than the %zu it has",
+                 d, lds, RB_FALL, lds_max);
+  if (lds > lds_default) {
+    static bool configured[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (!configured[dev]) {
+      MELD_HIP_CALL(hipFuncSetAttribute(reinterpret_cast<const void*>(&radius_exact_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)lds_max));
+      configured[dev] = true;
+    }
+  }
   // rows x reference chunks: about four workgroups per CU however few rows are flagged
   const int64_t n_groups = ceil_div(n_flag, RB_FALL);
   const int64_t want_chunks = std::max<int64_t>(1, 1024 / n_groups);
