@@ -465,48 +465,63 @@ int meld_csr_anisotropy_degrees(const int64_t* rowptr, const int32_t* col, doubl
  *      Graph.estimate_lmax] at meld/filter.py:39 and [UPSTREAM pygsp
  *      filters.approximations.cheby_op] at meld/filter.py:59) ------------------------------- */
 
-/* One step of the three-term recurrence on local rows [0, n_rows) of L = diag(dw) - W:
+/* The operator L = diag(dw) - W on the local rows [0, n_rows) of a row shard (all rows on one GPU), as every recurrence entry
+ * below takes it: the CSR arrays of W, the degrees, and optionally the panel-tiled copy of W (meld_pt_build, further down).
+ * layout != NULL selects the panel-tiled kernel (csrc/spmm_tiled.hip), NULL the CSR-stream kernel (csrc/spmm.hip); the entry
+ * points, their contracts and their call sites are the same.  rowptr and dw are always required; col and val when layout is
+ * NULL (and nnz > 0); every array of the layout otherwise.  nnz (total nonzeros of the local rows) sizes the CSR-stream
+ * kernel's LDS staging area.  The record and the layout it points to are HOST memory, read during the call only. */
+struct meld_pt_layout;
+typedef struct meld_laplacian {
+  const int64_t* rowptr; const int32_t* col; const double* val; const double* dw;
+  int64_t n_rows, nnz;
+  const struct meld_pt_layout* layout;   /* NULL: CSR-stream kernel; col/val may be NULL when set */
+} meld_laplacian_t;
+
+/* One step of the three-term recurrence on the local rows of L:
  *     y      = alpha * (dw .* x_loc - W x_full) + beta * x_loc + gamma * z
  *     r     += coef * y                      (if r != NULL)
  *     dots   = per-slot partial sums of [ <y, x_loc>, <y, y> ]   (if dots != NULL; p == 1 only;
  *              dots has 2 * meld_spmm_dot_slots() entries: slot-major per quantity; the caller
  *              sums the slots.  Used by the Lanczos lmax estimate.)
  * x_full is the full-length gathered vector ([n_cols, p] row-major), x_loc = x_full + x_row_offset*p,
- * z, y, r are local ([n_rows, p]); y may alias z.  z may be NULL when gamma == 0.
- * nnz_hint (total nonzeros of the local rows, or 0) only sizes the LDS staging area.
+ * z, y, r are local ([n_rows, p]); y may alias z.  z may be NULL when gamma == 0.  Any p >= 1 (the CSR-stream kernel in
+ * passes of 4 / 2 / 1 columns, the tiled one in passes of 2 + 1).
  *   T1 = (L s - a2 s)/a1          : alpha = 1/a1, beta = -a2/a1, gamma = 0
  *   Tk = (2/a1)(L - a2) T - Told  : alpha = 2/a1, beta = -2 a2/a1, gamma = -1  */
 int meld_spmm_dot_slots(void);
-int meld_cheby_step(const int64_t* rowptr, const int32_t* col, const double* val, const double* dw,
-                    int64_t n_rows, int64_t nnz_hint, int p, const double* x_full, int64_t x_row_offset,
-                    const double* z, double* y, double* r, double alpha, double beta, double gamma,
-                    double coef, double* dots, meld_stream_t stream);
+int meld_cheby_step(const meld_laplacian_t* L, int p, const double* x_full, int64_t x_row_offset, const double* z, double* y,
+                    double* r, double alpha, double beta, double gamma, double coef, double* dots, meld_stream_t stream);
 
 /* One step of the same recurrence for a WIDE signal (the probe block of the filter-bank VertexFrequencyCluster, stands in for the
  * dense window products of /root/reference/meld/cluster.py:98-156,179-194): 1 <= p <= 64 columns, row-major [rows, p], lanes =
  * columns -- the matrix is streamed once for all columns instead of once per column pair.  No accumulator, no dot products:
- *   y = alpha (dw .* x - W x) + beta x + gamma z     (y and z may alias) */
-int meld_cheby_step_wide(const int64_t* rowptr, const int32_t* col, const double* val, const double* dw, int64_t n_rows, int p,
-                         const double* x_full, int64_t x_row_offset, const double* z, double* y, double alpha, double beta,
-                         double gamma, meld_stream_t stream);
+ *   y = alpha (dw .* x - W x) + beta x + gamma z     (y and z may alias)
+ * Reads the CSR arrays of the record whatever its layout: col and val are required. */
+int meld_cheby_step_wide(const meld_laplacian_t* L, int p, const double* x_full, int64_t x_row_offset, const double* z, double* y,
+                         double alpha, double beta, double gamma, meld_stream_t stream);
 
 /* r = a * x  (n doubles) -- initialises r = c0/2 * T0 */
-/* Device-resident Lanczos iterations [it_begin, it_begin + n_iter) of L = diag(dw) - W (single GPU:
- * all n_rows rows local), for the lmax estimate ([UPSTREAM pygsp Graph.estimate_lmax], reference
- * meld/filter.py:39).  v0/v1/v2 [n_rows]: the three rotating vectors -- before iteration 0, v1 holds the
- * (un-normalised) start vector and v0 zeros; state[8]: state[0] = state[3] = 1 / |start|, the rest zero; scratch:
- * 3 * meld_spmm_dot_slots() doubles, zero before iteration 0.  alphas[it] / betas[it] receive the
- * tridiagonal entries; nothing is synchronised -- read them back when a convergence check is due. */
-int meld_lanczos_steps(const int64_t* rowptr, const int32_t* col, const double* val, const double* dw,
-                       int64_t n_rows, int64_t nnz_hint, double* v0, double* v1, double* v2, double* state,
-                       double* alphas, double* betas, int it_begin, int n_iter, double* scratch,
-                       meld_stream_t stream);
+/* Device-resident Lanczos iterations [it_begin, it_begin + n_iter) of L (single GPU: all n_rows rows local), for the lmax
+ * estimate ([UPSTREAM pygsp Graph.estimate_lmax], reference meld/filter.py:39).  v0/v1/v2 [n_rows]: the three rotating
+ * vectors -- before iteration 0, v1 holds the (un-normalised) start vector and v0 zeros; state[8]: state[0] = state[3] =
+ * 1 / |start|, the rest zero.  alphas[it] / betas[it] receive the tridiagonal entries; nothing is synchronised -- read them
+ * back when a convergence check is due.
+ *   CSR-stream kernel: scratch = 3 * meld_spmm_dot_slots() doubles, zero before iteration 0; stop is ignored.
+ *   tiled layout: scratch = 8 * meld_spmm_dot_slots() doubles (partial sums and scalars in parity buffers: two launches per
+ *     iteration, the SpMV derives its own scalars; only state[0] = 1 / |start| is read, before iteration 0); betas[it] of the
+ *     LAST iteration of a call is written by a closing one-wave launch.  stop (optional, device memory): a launch of the call
+ *     that finds *stop != 0 when it starts does nothing -- the caller checks convergence on the host while the NEXT batch
+ *     already runs and voids what is left of it once it has its answer (the vectors and the entries of that batch are then
+ *     undefined). */
+int meld_lanczos_steps(const meld_laplacian_t* L, double* v0, double* v1, double* v2, double* state, double* alphas,
+                       double* betas, int it_begin, int n_iter, double* scratch, const int32_t* stop, meld_stream_t stream);
 /* The same iteration as four stream-ordered phases, for the row-sharded driver (it all-reduces dots after
  * the SpMV and nrm2 after the axpy, and all-gathers the new vector): x_full is the gathered iterate,
  * x_row_offset the first local row in it; z_local / y_local / x_local are local rows; state / dots
- * (2 * slots) / nrm2 (slots) as in meld_lanczos_steps. */
-int meld_lanczos_spmv(const int64_t* rowptr, const int32_t* col, const double* val, const double* dw, int64_t n_rows,
-                      int64_t nnz_hint, const double* x_full, int64_t x_row_offset, const double* z_local,
+ * (2 * slots) / nrm2 (slots) as in meld_lanczos_steps (CSR-stream form).  On the tiled layout the SpMV streams the fp32
+ * copy of the values (pval32) when the layout keeps one. */
+int meld_lanczos_spmv(const meld_laplacian_t* L, const double* x_full, int64_t x_row_offset, const double* z_local,
                       double* y_local, const double* state, double* dots, meld_stream_t stream);
 int meld_lanczos_alpha(double* state, const double* dots, double* nrm2, double* alphas, int it, meld_stream_t stream);
 int meld_lanczos_axpy(const double* x_local, double* y_local, int64_t n_rows, const double* state, double* nrm2,
@@ -532,7 +547,7 @@ int meld_axpby_f64(double a, const double* x, double b, double* y, int64_t n, do
                    meld_stream_t stream);
 
 /* ---- panel-tiled, symmetry-folded layout of W for the recurrence (csrc/spmm_tiled.hip) ----------
- * Same operator and same call sites as meld_cheby_step / meld_lanczos_* ([UPSTREAM pygsp cheby_op /
+ * The `layout` of meld_laplacian_t: same operator and same entry points ([UPSTREAM pygsp cheby_op /
  * estimate_lmax] at reference meld/filter.py:59 / :39), on a copy of W laid out so that the iterate is
  * staged in LDS instead of being gathered per nonzero: rows in nb nnz-balanced blocks (one per CU); the
  * nonzeros whose column lies inside the block's own row range are stored once per symmetric pair (IN
@@ -559,7 +574,7 @@ typedef struct meld_pt_layout {
   const uint32_t* pidx;
   int32_t nb;
   const float* pval32; /* optional: pval rounded to fp32, streamed by the Lanczos SpMV of the lmax estimate
-                          (meld_pt_lanczos_*) instead of pval; NULL = not kept */
+                          (meld_lanczos_steps / meld_lanczos_spmv) instead of pval; NULL = not kept */
   int64_t stream_len;  /* entries of pval / pidx / pval32 (= meld_pt_stream_len(nnz, nb)) */
   const uint16_t* cdesc; /* [meld_pt_desc_len(nb)] chunk descriptors of every consumer wave's stream */
 } meld_pt_layout_t;
@@ -568,10 +583,6 @@ int meld_pt_num_blocks(int64_t n_rows); /* nb the builder wants for n_rows local
 int64_t meld_pt_seg_len(int nb);
 int64_t meld_pt_stream_len(int64_t nnz, int nb);
 int64_t meld_pt_desc_len(int nb);
-/* timing-only ablations of the step kernel (tools/spmm_compare.py); results are wrong while mask != 0 */
-int meld_pt_debug_ablate(int mask);
-/* development: per-wave wall-clock stamps of the following step launches into buf[nb][16][8] (NULL: off) */
-int meld_pt_debug_stamps(unsigned long long* buf);
 /* Build the layout of the local rows [0, n_rows) of a CSR matrix with n_cols columns (the arrays of
  * `layout` are written); local row r is column col_base + r of the matrix (0 on one GPU, the shard's first
  * row on a row shard); symmetric != 0 folds the in-block pairs.  status[0] (device) receives 0, or the
@@ -579,35 +590,10 @@ int meld_pt_debug_stamps(unsigned long long* buf);
  * 1 = (no longer raised: a block's column panels are handled in groups), 2 = too many distinct columns in a block,
  * 3 = n_cols beyond the builder's index range, 4 = a segment / a wave's pairs / its padding beyond the
  * builder's ranges, 5 = W is not bitwise symmetric inside a block (build again with symmetric = 0),
- * 6 = a diagonal entry -- the caller then stays on meld_cheby_step. */
+ * 6 = a diagonal entry -- the caller then leaves `layout` of its operator record NULL. */
 int meld_pt_build(const int64_t* rowptr, const int32_t* col, const double* val, int64_t n_rows, int64_t n_cols,
                   int64_t col_base, int symmetric, const meld_pt_layout_t* layout,
                   uint32_t* codes /* scratch, nnz entries */, int32_t* status, meld_stream_t stream);
-/* meld_cheby_step on the layout (p = 1, 2 or any p as passes of 2 + 1 columns; dots as there). */
-int meld_pt_cheby_step(const meld_pt_layout_t* layout, const int64_t* rowptr, const double* dw, int64_t n_rows, int p,
-                       const double* x_full, int64_t x_row_offset, const double* z, double* y, double* r,
-                       double alpha, double beta, double gamma, double coef, double* dots, meld_stream_t stream);
-/* Steps 2 .. n_coef - 1 of the Chebyshev recurrence in one call (single GPU, no collective between the steps):
- *   T_k = alpha2 L T_{k-1} + beta2 T_{k-1} - T_{k-2},   r += coeffs[k] T_k      [UPSTREAM pygsp cheby_op, /root/reference/meld/filter.py:59]
- * t_prev2 / t_prev1: [n_rows, p] buffers holding T_0 / T_1 on entry, used as ping-pong buffers; r: holds c_0/2 T_0 + c_1 T_1 on
- * entry, the filtered signal on return; coeffs: n_coef doubles on the HOST.  The accumulator is read and written every other step
- * only (a step adds c_k T_k + c_{k-1} T_{k-1} at once), which removes 16 of the 80 vector bytes per row and step at p = 2.
- * *last (optional) = 1 if t_prev1 holds the last T, 0 if t_prev2 does. */
-int meld_pt_cheby_run(const meld_pt_layout_t* layout, const int64_t* rowptr, const double* dw, int64_t n_rows, int p,
-                      double* t_prev2, double* t_prev1, double* r, const double* coeffs, int n_coef, double alpha2, double beta2,
-                      int* last, meld_stream_t stream);
-/* meld_lanczos_steps / meld_lanczos_spmv on the layout.  Same contracts, except that meld_pt_lanczos_steps needs
- * scratch = 8 * meld_spmm_dot_slots() doubles (it keeps its partial sums and scalars in parity buffers there: two launches per
- * iteration, the SpMV derives its own scalars; only state[0] = 1 / |start| is read, before iteration 0) and that betas[it] of
- * the LAST iteration of a call is written by a closing one-wave launch.  stop (optional, device memory): a launch of the call that
- * finds *stop != 0 when it starts does nothing -- the caller checks convergence on the host while the NEXT batch already runs
- * and voids what is left of it once it has its answer (the vectors and the entries of that batch are then undefined). */
-int meld_pt_lanczos_steps(const meld_pt_layout_t* layout, const int64_t* rowptr, const double* dw, int64_t n_rows,
-                          double* v0, double* v1, double* v2, double* state, double* alphas, double* betas,
-                          int it_begin, int n_iter, double* scratch, const int32_t* stop, meld_stream_t stream);
-int meld_pt_lanczos_spmv(const meld_pt_layout_t* layout, const int64_t* rowptr, const double* dw, int64_t n_rows,
-                         const double* x_full, int64_t x_row_offset, const double* z_local, double* y_local,
-                         const double* state, double* dots, meld_stream_t stream);
 
 /* ---- row-sharded recurrences with the host out of the loop (csrc/sharded.hip) ----------
  * One process per GPU, cells row-sharded: rank g owns rows [g * rows_pad, (g + 1) * rows_pad) of every full-length vector.
@@ -622,22 +608,24 @@ int meld_rccl_comm_create(const void* id_host, int world, int rank, void** comm)
 int meld_rccl_comm_destroy(void* comm);
 int meld_rccl_all_gather(void* comm, const void* send, void* recv, size_t bytes_per_rank, meld_stream_t stream);
 int meld_rccl_all_reduce_sum_f64(void* comm, double* buf, size_t count, meld_stream_t stream);
-/* Steps 2 .. n_coef - 1 of the Chebyshev recurrence on a row shard in ONE call (meld_pt_cheby_run's contract with a row
- * offset and an all-gather behind every step): t_a / t_b are the FULL-length iterates [world * rows_pad, p] holding the
- * gathered T_0 / T_1, r [rows_pad, p] the local rows of the result.  layout: the shard's panel-tiled layout, or NULL for
- * the CSR-stream kernel (col / val read only then).  coeffs on the HOST.  Replaces one kernel call + one
- * torch.distributed all-gather per step issued from Python. */
-int meld_cheby_run_sharded(void* comm, const meld_pt_layout_t* layout, const int64_t* rowptr, const int32_t* col, const double* val,
-                           const double* dw, int64_t n_rows, int64_t nnz, int64_t rows_pad, int64_t row_begin, int p, double* t_a,
-                           double* t_b, double* r, const double* coeffs, int n_coef, double alpha2, double beta2, int* last,
-                           meld_stream_t stream);
+/* Steps 2 .. n_coef - 1 of the Chebyshev recurrence in ONE call:
+ *   T_k = alpha2 L T_{k-1} + beta2 T_{k-1} - T_{k-2},   r += coeffs[k] T_k      [UPSTREAM pygsp cheby_op, reference meld/filter.py:59]
+ * t_a / t_b are the FULL-length iterates [world * rows_pad, p] holding the gathered T_0 / T_1 on entry, used as ping-pong
+ * buffers (T_k overwrites the local rows of T_{k-2}); r [rows_pad, p]: the local rows of the result, holding c_0/2 T_0 + c_1 T_1
+ * on entry; coeffs: n_coef doubles on the HOST.  comm: the rank's communicator (meld_rccl_comm_create) -- the new local slice
+ * is all-gathered in place behind every step, row_begin = rank * rows_pad -- or NULL on a single GPU: no collective, row_begin
+ * must be 0.  Replaces one kernel call (+ one torch.distributed all-gather) per step issued from Python.  On the tiled layout
+ * the accumulator is read and written every other step only (a step adds c_k T_k + c_{k-1} T_{k-1} at once), which removes 16
+ * of the 80 vector bytes per row and step at p = 2; the CSR-stream kernel adds c_k T_k at every step.
+ * *last (optional) = 1 if t_b holds the last T, 0 if t_a does. */
+int meld_cheby_run(void* comm, const meld_laplacian_t* L, int64_t rows_pad, int64_t row_begin, int p, double* t_a, double* t_b,
+                   double* r, const double* coeffs, int n_coef, double alpha2, double beta2, int* last, meld_stream_t stream);
 /* Iterations [it_begin, it_begin + n_iter) of the one-reduction Lanczos recurrence (meld_lanczos_spmv with state[3] = 1,
  * state[4] = 0; ONE all-reduce of acc [3 * meld_spmm_dot_slots()]; meld_lanczos_fold; meld_lanczos_axpy3; all-gather of
  * the new vector) on a row shard in one call.  v0 / v1 / v2: FULL-length rotating vectors [world * rows_pad]. */
-int meld_lanczos_steps_sharded(void* comm, const meld_pt_layout_t* layout, const int64_t* rowptr, const int32_t* col,
-                               const double* val, const double* dw, int64_t n_rows, int64_t nnz, int64_t rows_pad, int64_t row_begin,
-                               double* v0, double* v1, double* v2, double* state, double* acc, double* alphas, double* betas,
-                               int it_begin, int n_iter, meld_stream_t stream);
+int meld_lanczos_steps_sharded(void* comm, const meld_laplacian_t* L, int64_t rows_pad, int64_t row_begin, double* v0, double* v1,
+                               double* v2, double* state, double* acc, double* alphas, double* betas, int it_begin, int n_iter,
+                               meld_stream_t stream);
 
 /* ---- KMeans step of VertexFrequencyCluster.predict (reference meld/cluster.py:315-345 -> [UPSTREAM
  *      sklearn.cluster.KMeans], Lloyd iteration; csrc/kmeans.hip) ---------------------------------------

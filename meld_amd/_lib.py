@@ -111,12 +111,10 @@ SIGNATURES = {
     "meld_csr_anisotropy": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _i64, _f64, _ptr]),
     "meld_csr_anisotropy_degrees": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _i64, _f64, _ptr, _ptr]),
     "meld_spmm_dot_slots": (_i32, []),
-    "meld_cheby_step": (
-        _i32,
-        [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i32, _ptr, _i64, _ptr, _ptr, _ptr, _f64, _f64, _f64, _f64, _ptr, _ptr],
-    ),
-    "meld_lanczos_steps": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr, _ptr]),
-    "meld_lanczos_spmv": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    # (the first _ptr of the recurrence entries: a Laplacian record, by reference)
+    "meld_cheby_step": (_i32, [_ptr, _i32, _ptr, _i64, _ptr, _ptr, _ptr, _f64, _f64, _f64, _f64, _ptr, _ptr]),
+    "meld_lanczos_steps": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr, _ptr, _ptr]),
+    "meld_lanczos_spmv": (_i32, [_ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "meld_lanczos_alpha": (_i32, [_ptr, _ptr, _ptr, _ptr, _i32, _ptr]),
     "meld_lanczos_axpy": (_i32, [_ptr, _ptr, _i64, _ptr, _ptr, _ptr]),
     "meld_lanczos_beta": (_i32, [_ptr, _ptr, _ptr, _ptr, _i32, _ptr]),
@@ -125,16 +123,10 @@ SIGNATURES = {
     "meld_pt_geometry": (_i32, [_ptr, _ptr, _ptr, _ptr]),
     "meld_pt_num_blocks": (_i32, [_i64]),
     "meld_pt_seg_len": (_i64, [_i32]),
-    "meld_pt_debug_ablate": (_i32, [_i32]),
-    "meld_pt_debug_stamps": (_i32, [_ptr]),
     "meld_pt_stream_len": (_i64, [_i64, _i32]),
     "meld_pt_desc_len": (_i64, [_i32]),
     "meld_pt_build": (_i32, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i32, _ptr, _ptr, _ptr, _ptr]),
-    "meld_cheby_step_wide": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _i32, _ptr, _i64, _ptr, _ptr, _f64, _f64, _f64, _ptr]),
-    "meld_pt_cheby_step": (_i32, [_ptr, _ptr, _ptr, _i64, _i32, _ptr, _i64, _ptr, _ptr, _ptr, _f64, _f64, _f64, _f64, _ptr, _ptr]),
-    "meld_pt_cheby_run": (_i32, [_ptr, _ptr, _ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr, _i32, _f64, _f64, _ptr, _ptr]),
-    "meld_pt_lanczos_steps": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr, _ptr, _ptr]),
-    "meld_pt_lanczos_spmv": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "meld_cheby_step_wide": (_i32, [_ptr, _i32, _ptr, _i64, _ptr, _ptr, _f64, _f64, _f64, _ptr]),
     "meld_kmeans_max_blocks": (_i32, []),
     "meld_kmeans_assign": (_i32, [_ptr, _i64, _i32, _ptr, _i32, _ptr, _ptr, _ptr, _ptr, _i32, _ptr]),
     "meld_scale_f64": (_i32, [_ptr, _f64, _ptr, _i64, _ptr]),
@@ -157,8 +149,8 @@ SIGNATURES = {
     "meld_rccl_comm_destroy": (_i32, [_ptr]),
     "meld_rccl_all_gather": (_i32, [_ptr, _ptr, _ptr, _sz, _ptr]),
     "meld_rccl_all_reduce_sum_f64": (_i32, [_ptr, _ptr, _sz, _ptr]),
-    "meld_cheby_run_sharded": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _i32, _ptr, _ptr, _ptr, _ptr, _i32, _f64, _f64, _ptr, _ptr]),
-    "meld_lanczos_steps_sharded": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr]),
+    "meld_cheby_run": (_i32, [_ptr, _ptr, _i64, _i64, _i32, _ptr, _ptr, _ptr, _ptr, _i32, _f64, _f64, _ptr, _ptr]),
+    "meld_lanczos_steps_sharded": (_i32, [_ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr]),
     "meld_factorize_max_groups": (_i32, []),
     "meld_factorize_max_words": (_i32, []),
     "meld_factorize_temp_bytes": (_sz, [_i64]),
@@ -169,12 +161,20 @@ SIGNATURES = {
 }
 
 
-
 class PtLayout(C.Structure):
     """``meld_pt_layout_t`` of include/meld_hip.h (device pointers of the panel-tiled copy of W)."""
 
     _fields_ = [("blk_row", _ptr), ("blk_ntile", _ptr), ("blk_ndist", _ptr), ("seg", _ptr), ("list_cols", _ptr),
                 ("pval", _ptr), ("pidx", _ptr), ("nb", C.c_int32), ("pval32", _ptr), ("stream_len", C.c_int64), ("cdesc", _ptr)]
+
+
+class Laplacian(C.Structure):
+    """``meld_laplacian_t`` of include/meld_hip.h: the operator every recurrence entry takes (device pointers of the CSR arrays
+    and the degrees; ``layout`` NULL selects the CSR-stream kernel).  Holds addresses only: the owner keeps the tensors and
+    the ``PtLayout`` alive."""
+
+    _fields_ = [("rowptr", _ptr), ("col", _ptr), ("val", _ptr), ("dw", _ptr), ("n_rows", C.c_int64), ("nnz", C.c_int64),
+                ("layout", C.POINTER(PtLayout))]
 
 
 _lib = None

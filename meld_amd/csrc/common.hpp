@@ -75,6 +75,15 @@ struct PtLanczos {
   const int* stop;  // (optional) nonzero when the launch starts: it does nothing (a stop request of the host's convergence check)
 };
 
+// the null-pointer checks of an operator record (include/meld_hip.h): rowptr and dw always, the arrays of the layout when it
+// is set, col and val otherwise (a matrix without entries has none)
+static inline bool laplacian_ok(const meld_laplacian_t* L) {
+  if (!L || !L->rowptr || !L->dw) return false;
+  if (const meld_pt_layout_t* t = L->layout)
+    return t->blk_row && t->blk_ntile && t->blk_ndist && t->seg && t->list_cols && t->pval && t->pidx;
+  return L->nnz == 0 || (L->col && L->val);
+}
+
 // one recurrence step on the panel-tiled layout (spmm_tiled.hip); coef_dev: device-resident Lanczos scalars
 int pt_step(const meld_pt_layout_t* L, const int64_t* rowptr, const double* dw, int p, const double* x_full,
             int64_t x_row_offset, const double* z, double* y, double* r, double alpha, double beta, double gamma,

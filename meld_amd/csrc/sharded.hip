@@ -1,5 +1,6 @@
 // sharded.hip -- the row-sharded recurrences with the host out of the loop ("RCCL calls issued
-// ... from C with a passed ncclComm_t").
+// ... from C with a passed ncclComm_t"), and the one Chebyshev loop of the library (meld_cheby_run: the same steps with or
+// without a communicator).
 //
 // One process per GPU; cells are row-sharded (meld_amd/distributed.py).  A Chebyshev step / a Lanczos iteration on a shard is
 // one kernel over the local rows followed by an all-gather of the new local slice of the iterate (+ ONE all-reduce of partial
@@ -139,70 +140,61 @@ extern "C" int meld_rccl_all_reduce_sum_f64(void* comm, double* buf, size_t coun
   return MELD_OK;
 }
 
-// Steps k = 2 .. n_coef - 1 of the Chebyshev recurrence on a row shard, in one call:
+// Steps k = 2 .. n_coef - 1 of the Chebyshev recurrence in one call, on a row shard (comm) or a single GPU (comm == NULL):
 //   T_k(local rows) = alpha2 L T_{k-1} + beta2 T_{k-1} - T_{k-2};  r += c_k T_k;  all-gather of the local slice of T_k
 // [UPSTREAM pygsp cheby_op, reference meld/filter.py:59; the partitioning of SURVEY.md section 8e].
 // t_a / t_b: the two FULL-length iterates [world * rows_pad, p] holding T_0 / T_1 (gathered) on entry, used as ping-pong
 // buffers (T_k overwrites the local rows of T_{k-2}, then the slices are gathered in place); r [rows_pad, p]: the local rows
-// of the result, already holding c_0 / 2 T_0 + c_1 T_1.  layout: the shard's panel-tiled layout, or NULL for the CSR-stream
-// kernel (col / val are only read then).  On the tiled kernel the accumulator is touched every other step (as
-// meld_pt_cheby_run).  coeffs: n_coef doubles on the HOST.  *last (optional) = 1 if t_b holds the last T, 0 if t_a does.
-extern "C" int meld_cheby_run_sharded(void* comm, const meld_pt_layout_t* layout, const int64_t* rowptr, const int32_t* col,
-                                      const double* val, const double* dw, int64_t n_rows, int64_t nnz, int64_t rows_pad,
-                                      int64_t row_begin, int p, double* t_a, double* t_b, double* r, const double* coeffs,
-                                      int n_coef, double alpha2, double beta2, int* last, meld_stream_t stream) {
-  MELD_CHECK_ARG(comm && rowptr && dw && t_a && t_b && r && coeffs && n_rows >= 0 && rows_pad >= n_rows && row_begin >= 0 &&
-                     p >= 1 && n_coef >= 2 && (layout || (col && val) || n_rows == 0),
-                 "meld_cheby_run_sharded: bad arguments");
-  Comm* c = reinterpret_cast<Comm*>(comm);
-  MELD_CHECK_ARG(row_begin == (int64_t)c->rank * rows_pad, "meld_cheby_run_sharded: row_begin %lld is not rank %d's slice of %lld rows",
-                 (long long)row_begin, c->rank, (long long)rows_pad);
+// of the result, already holding c_0 / 2 T_0 + c_1 T_1.  On the tiled layout the accumulator is touched every OTHER step
+// only: a step that holds T_k in its result and T_{k-1} in its own rows of the iterate adds c_k T_k + c_{k-1} T_{k-1} at
+// once, the step before it neither reads nor writes r -- 32 of the 80 bytes of vector traffic per row and step pair at
+// p = 2.  coeffs: n_coef doubles on the HOST.  *last (optional) = 1 if t_b holds the last T, 0 if t_a does.
+extern "C" int meld_cheby_run(void* comm, const meld_laplacian_t* L, int64_t rows_pad, int64_t row_begin, int p, double* t_a,
+                              double* t_b, double* r, const double* coeffs, int n_coef, double alpha2, double beta2, int* last,
+                              meld_stream_t stream) {
+  MELD_CHECK_ARG(laplacian_ok(L) && t_a && t_b && r && coeffs && L->n_rows >= 0 && rows_pad >= L->n_rows && row_begin >= 0 && p >= 1 &&
+                     n_coef >= 2,
+                 "meld_cheby_run: bad arguments");
+  Comm* c = reinterpret_cast<Comm*>(comm);  // NULL: a single GPU, nothing to gather
+  const int rank = c ? c->rank : 0;
+  MELD_CHECK_ARG(row_begin == (int64_t)rank * rows_pad, "meld_cheby_run: row_begin %lld is not rank %d's slice of %lld rows",
+                 (long long)row_begin, rank, (long long)rows_pad);
   hipStream_t st = S(stream);
   double* t_old = t_a;
   double* t_cur = t_b;
   int which = 1;
   const size_t slice = (size_t)rows_pad * p * sizeof(double);
-  auto step = [&](int k, bool touch_r, double coef, double coef_x) -> int {
+  // one step; tiled layout: r += coef T_k + coef_x T_{k-1} when touch_r, left alone otherwise
+  auto step = [&](bool touch_r, double coef, double coef_x) -> int {
     double* loc = t_old + (size_t)row_begin * p;  // T_k overwrites the local rows of T_{k-2} (z and y alias)
-    if (n_rows > 0) {
-      if (layout) {
-        const int rc = pt_step(layout, rowptr, dw, p, t_cur, row_begin, loc, loc, touch_r ? r : nullptr, alpha2, beta2, -1.0, coef,
-                               nullptr, nullptr, st, coef_x);
-        if (rc != MELD_OK) return rc;
-      } else {
-        const int rc = meld_cheby_step(rowptr, col, val, dw, n_rows, nnz, p, t_cur, row_begin, loc, loc, r, alpha2, beta2, -1.0,
-                                       coeffs[k], nullptr, stream);
-        if (rc != MELD_OK) return rc;
-      }
+    int rc = MELD_OK;
+    if (L->n_rows > 0) {
+      rc = L->layout ? pt_step(L->layout, L->rowptr, L->dw, p, t_cur, row_begin, loc, loc, touch_r ? r : nullptr, alpha2, beta2,
+                               -1.0, coef, nullptr, nullptr, st, coef_x)
+                     : meld_cheby_step(L, p, t_cur, row_begin, loc, loc, r, alpha2, beta2, -1.0, coef, nullptr, stream);
     }
-    const int rc = gather_in_place(c, t_old, slice, st);
-    if (rc != MELD_OK) return rc;
+    if (rc == MELD_OK && c) rc = gather_in_place(c, t_old, slice, st);
     std::swap(t_old, t_cur);
     which ^= 1;
-    return MELD_OK;
+    return rc;
   };
+  // steps that add their own c_k T_k: all of them on the CSR-stream kernel (it has no coef_x), on the tiled layout the first
+  // one of an odd number of steps; the rest go in pairs
+  const int alone = L->layout ? (n_coef - 2) % 2 : n_coef - 2;
   int k = 2;
-  if (!layout) {
-    for (; k < n_coef; ++k) {
-      const int rc = step(k, true, coeffs[k], 0.0);
-      if (rc != MELD_OK) return rc;
-    }
-  } else {
-    if ((n_coef - 2) % 2 == 1) {  // an odd number of steps: the first one alone
-      const int rc = step(k, true, coeffs[k], 0.0);
-      if (rc != MELD_OK) return rc;
-      ++k;
-    }
-    for (; k + 1 < n_coef; k += 2) {
-      int rc = step(k, false, 0.0, 0.0);  // T_k: no accumulator traffic
-      if (rc != MELD_OK) return rc;
-      // T_{k+1}, and r += c_{k+1} T_{k+1} + c_k T_k (T_k = this step's own rows of the gathered iterate)
-      rc = step(k + 1, true, coeffs[k + 1], coeffs[k]);
-      if (rc != MELD_OK) return rc;
-    }
+  for (; k < 2 + alone; ++k) {
+    const int rc = step(true, coeffs[k], 0.0);
+    if (rc != MELD_OK) return rc;
+  }
+  for (; k + 1 < n_coef; k += 2) {
+    int rc = step(false, 0.0, 0.0);  // T_k: no accumulator traffic
+    if (rc != MELD_OK) return rc;
+    // T_{k+1}, and r += c_{k+1} T_{k+1} + c_k T_k (T_k = this step's own rows of the gathered iterate)
+    rc = step(true, coeffs[k + 1], coeffs[k]);
+    if (rc != MELD_OK) return rc;
   }
   if (last) *last = which;
-  MELD_LAUNCH_CHECK("meld_cheby_run_sharded");
+  MELD_LAUNCH_CHECK("meld_cheby_run");
   return MELD_OK;
 }
 
@@ -211,12 +203,11 @@ extern "C" int meld_cheby_run_sharded(void* comm, const meld_pt_layout_t* layout
 // one call: per iteration the SpMV of the local rows, ONE all-reduce of the 3 x slots partial sums, the one-wave scalar kernel,
 // the three-term update and the all-gather of the new vector.  v0 / v1 / v2: FULL-length rotating vectors [world * rows_pad];
 // state [8], acc [3 * meld_spmm_dot_slots()], alphas / betas as for the phase entry points.
-extern "C" int meld_lanczos_steps_sharded(void* comm, const meld_pt_layout_t* layout, const int64_t* rowptr, const int32_t* col,
-                                          const double* val, const double* dw, int64_t n_rows, int64_t nnz, int64_t rows_pad,
-                                          int64_t row_begin, double* v0, double* v1, double* v2, double* state, double* acc,
-                                          double* alphas, double* betas, int it_begin, int n_iter, meld_stream_t stream) {
-  MELD_CHECK_ARG(comm && rowptr && dw && v0 && v1 && v2 && state && acc && alphas && betas && n_rows >= 0 && rows_pad >= n_rows &&
-                     it_begin >= 0 && n_iter >= 0 && (layout || (col && val) || n_rows == 0),
+extern "C" int meld_lanczos_steps_sharded(void* comm, const meld_laplacian_t* L, int64_t rows_pad, int64_t row_begin, double* v0,
+                                          double* v1, double* v2, double* state, double* acc, double* alphas, double* betas,
+                                          int it_begin, int n_iter, meld_stream_t stream) {
+  MELD_CHECK_ARG(comm && laplacian_ok(L) && v0 && v1 && v2 && state && acc && alphas && betas && L->n_rows >= 0 &&
+                     rows_pad >= L->n_rows && it_begin >= 0 && n_iter >= 0,
                  "meld_lanczos_steps_sharded: bad arguments");
   Comm* c = reinterpret_cast<Comm*>(comm);
   MELD_CHECK_ARG(row_begin == (int64_t)c->rank * rows_pad, "meld_lanczos_steps_sharded: row_begin is not this rank's slice");
@@ -228,11 +219,7 @@ extern "C" int meld_lanczos_steps_sharded(void* comm, const meld_pt_layout_t* la
     double* u_prev = V[k % 3];
     double* u = V[(k + 1) % 3];
     double* y = V[(k + 2) % 3];
-    int rc;
-    if (layout)
-      rc = meld_pt_lanczos_spmv(layout, rowptr, dw, n_rows, u, row_begin, u_prev + row_begin, y + row_begin, state, acc, stream);
-    else
-      rc = meld_lanczos_spmv(rowptr, col, val, dw, n_rows, nnz, u, row_begin, u_prev + row_begin, y + row_begin, state, acc, stream);
+    int rc = meld_lanczos_spmv(L, u, row_begin, u_prev + row_begin, y + row_begin, state, acc, stream);
     if (rc != MELD_OK) return rc;
     MELD_RCCL_CALL(rc_.AllReduce(acc, acc, (size_t)3 * slots, NCCL_FLOAT64, NCCL_SUM, c->comm, st), "ncclAllReduce");
     rc = meld_lanczos_fold(state, acc, alphas, betas, k, stream);

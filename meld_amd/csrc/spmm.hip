@@ -18,8 +18,6 @@
 // registers.  HBM-bound: 12 B/nonzero streamed + vector traffic (roofline section).
 #include "common.hpp"
 
-#include <cstdlib>
-
 #include <algorithm>
 
 namespace meld {
@@ -60,9 +58,7 @@ __device__ __forceinline__ void store_row(double* __restrict__ base, int64_t row
   }
 }
 
-#ifndef SPMM_U
-#define SPMM_U 8  // (value, column, gather) chains in flight per thread (measured at 1M, P = 2: 2 -> 224, 4 -> 206, 8 -> 194 us)
-#endif
+constexpr int SPMM_U = 8;  // (value, column, gather) chains in flight per thread (measured at 1M, P = 2: 2 -> 224, 4 -> 206, 8 -> 194 us)
 
 template <int P, int RB>
 __global__ __launch_bounds__(256) void cheby_step_kernel(
@@ -274,7 +270,7 @@ __global__ __launch_bounds__(256) void lanczos_axpy_fused_kernel(double* __restr
   __syncthreads();
   if (threadIdx.x == 0) atomicAdd(&nrm2[blockIdx.x % DOT_SLOTS], s_part[0] + s_part[1] + s_part[2] + s_part[3]);
 }
-// Device-resident loop on the tiled layout (meld_pt_lanczos_steps): no scalar kernel between the iterations.  The SpMV derives
+// Device-resident loop on the tiled layout (meld_lanczos_steps): no scalar kernel between the iterations.  The SpMV derives
 // s_k and beta_{k-1} itself (PtLanczos, common.hpp); this is the axpy of lanczos_axpy_fused_kernel with the parity buffers of
 // that scheme: it reads s_k from state_cur, <y, u> from dots_cur, adds |w|^2 into nrm2_cur (cleared by the SpMV before it) and
 // clears dots_next, the slots the NEXT SpMV adds into.
@@ -391,16 +387,25 @@ __global__ __launch_bounds__(256) void lanczos_axpy3_kernel(double* __restrict__
   if (threadIdx.x == 0) atomicAdd(&nrm2[blockIdx.x % DOT_SLOTS], s_part[0] + s_part[1] + s_part[2] + s_part[3]);
 }
 
-template <int P, int RB>
-static int launch_cheby(const int64_t* rowptr, const int32_t* col, const double* val, const double* dw, int64_t n_rows,
-                        int ld, int colofs, const double* x_full, int64_t x_row_offset, const double* z, double* y,
-                        double* r, double alpha, double beta, double gamma, double coef, double* dots, int chunk,
-                        hipStream_t st, const double* coef_dev = nullptr) {
-  const unsigned grid = (unsigned)(ceil_div(ceil_div(n_rows, RB), 8) * 8);  // multiple of 8: bijective XCD remap
+constexpr int CSR_RB = 32;  // rows per workgroup of the CSR-stream kernel
+
+// LDS chunk of the CSR-stream kernel: ~1.3x the mean span of CSR_RB rows, a multiple of 256 within [512, 48 KiB of products]
+static int csr_chunk(const meld_laplacian_t* L, int P) {
+  const double mean_span = (L->nnz > 0) ? (double)L->nnz / (double)L->n_rows * CSR_RB : 1024.0;
+  const int64_t c = (int64_t)(mean_span * 1.3) / 256 * 256 + 256;
+  const int64_t cmax = (48 * 1024) / (8 * P) / 256 * 256;
+  return (int)std::max<int64_t>(512, std::min<int64_t>(c, cmax));
+}
+
+template <int P>
+static void launch_cheby(const meld_laplacian_t* L, int ld, int colofs, const double* x_full, int64_t x_row_offset, const double* z,
+                         double* y, double* r, double alpha, double beta, double gamma, double coef, double* dots, hipStream_t st,
+                         const double* coef_dev = nullptr) {
+  const unsigned grid = (unsigned)(ceil_div(ceil_div(L->n_rows, CSR_RB), 8) * 8);  // multiple of 8: bijective XCD remap
+  const int chunk = csr_chunk(L, P);
   const size_t lds = sizeof(double) * (size_t)chunk * P;
-  hipLaunchKernelGGL((cheby_step_kernel<P, RB>), dim3(grid), dim3(256), lds, st, rowptr, col, val, dw, n_rows, ld,
+  hipLaunchKernelGGL((cheby_step_kernel<P, CSR_RB>), dim3(grid), dim3(256), lds, st, L->rowptr, L->col, L->val, L->dw, L->n_rows, ld,
                      colofs, x_full, x_row_offset, z, y, r, alpha, beta, gamma, coef, dots, chunk, coef_dev);
-  return 0;
 }
 
 // Wide signals (the probe block of the filter-bank VertexFrequencyCluster, p = 64 columns): lanes = COLUMNS.  A wave owns a row at
@@ -411,14 +416,8 @@ static int launch_cheby(const int64_t* rowptr, const int32_t* col, const double*
 // scalar operand of the FMA); eight gathers in flight per lane.  Rows of a workgroup are consecutive and workgroups are
 // XCD-contiguous, so the rows of the iterate a neighbourhood shares are served by that XCD's L2.
 //     y = alpha (dw .* x - W x) + beta x + gamma z      (y and z may alias: read before write per element)
-#ifndef MELD_WIDE_U
-#define MELD_WIDE_U 16
-#endif
-#ifndef MELD_WIDE_ROWS
-#define MELD_WIDE_ROWS 8
-#endif
-constexpr int WIDE_U = MELD_WIDE_U;        // gathers in flight per lane
-constexpr int WIDE_ROWS = MELD_WIDE_ROWS;  // rows per wave (consecutive)
+constexpr int WIDE_U = 16;    // gathers in flight per lane
+constexpr int WIDE_ROWS = 8;  // rows per wave (consecutive)
 __global__ __launch_bounds__(256) void cheby_step_wide_kernel(const int64_t* __restrict__ rowptr, const int* __restrict__ col,
                                                               const double* __restrict__ val, const double* __restrict__ dw,
                                                               int64_t n_rows, int p, const double* __restrict__ x_full,
@@ -527,67 +526,49 @@ __global__ __launch_bounds__(256) void cheby_step_wide_kernel(const int64_t* __r
 
 using namespace meld;
 
-// One step of the recurrence for a WIDE signal, 3 <= p <= 64 columns, row-major [rows, p] (lanes = columns; see
+// One step of the recurrence for a WIDE signal, 1 <= p <= 64 columns, row-major [rows, p] (lanes = columns; see
 // cheby_step_wide_kernel).  Same operator as meld_cheby_step without the accumulator and the dot products:
 //   y = alpha (dw .* x - W x) + beta x + gamma z;   x_full: the whole iterate [n_total, p], x_row_offset: first local row in it.
-extern "C" int meld_cheby_step_wide(const int64_t* rowptr, const int32_t* col, const double* val, const double* dw, int64_t n_rows,
-                                    int p, const double* x_full, int64_t x_row_offset, const double* z, double* y, double alpha,
-                                    double beta, double gamma, meld_stream_t stream) {
-  MELD_CHECK_ARG(rowptr && col && val && dw && x_full && y && n_rows >= 0 && p >= 1 && p <= 64, "meld_cheby_step_wide: bad arguments (1 <= p <= 64)");
+// Streams the CSR arrays of the record, whatever its layout.
+extern "C" int meld_cheby_step_wide(const meld_laplacian_t* L, int p, const double* x_full, int64_t x_row_offset, const double* z,
+                                    double* y, double alpha, double beta, double gamma, meld_stream_t stream) {
+  MELD_CHECK_ARG(L && L->rowptr && L->col && L->val && L->dw && x_full && y && L->n_rows >= 0 && p >= 1 && p <= 64,
+                 "meld_cheby_step_wide: bad arguments (1 <= p <= 64)");
   MELD_CHECK_ARG(gamma == 0.0 || z != nullptr, "meld_cheby_step_wide: z is required when gamma != 0");
-  if (n_rows == 0) return MELD_OK;
-  const int64_t nblk = ceil_div(n_rows, 4 * WIDE_ROWS);
+  if (L->n_rows == 0) return MELD_OK;
+  const int64_t nblk = ceil_div(L->n_rows, 4 * WIDE_ROWS);
   const unsigned grid = (unsigned)(ceil_div(nblk, 8) * 8);
-  // (profiling hook, never set in production: MELD_WIDE_PADLDS=<bytes> of unused dynamic LDS lowers the workgroups per CU, i.e. the
-  // rows in flight per XCD -- the window of the iterate its L2 has to hold)
-  static const size_t pad_lds = [] { const char* e = meld_dev_getenv("MELD_WIDE_PADLDS"); return e ? (size_t)atoi(e) : (size_t)0; }();
-  if (pad_lds > 65536) {
-    static bool done = false;
-    if (!done) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&cheby_step_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pad_lds); done = true; }
-  }
-  hipLaunchKernelGGL(cheby_step_wide_kernel, dim3(grid), dim3(256), pad_lds, S(stream), rowptr, col, val, dw, n_rows, p, x_full, x_row_offset, z,
-                     y, alpha, beta, gamma);
+  hipLaunchKernelGGL(cheby_step_wide_kernel, dim3(grid), dim3(256), 0, S(stream), L->rowptr, L->col, L->val, L->dw, L->n_rows, p, x_full,
+                     x_row_offset, z, y, alpha, beta, gamma);
   MELD_LAUNCH_CHECK("cheby_step_wide_kernel");
   return MELD_OK;
 }
 
 extern "C" int meld_spmm_dot_slots(void) { return DOT_SLOTS; }
 
-extern "C" int meld_cheby_step(const int64_t* rowptr, const int32_t* col, const double* val, const double* dw,
-                               int64_t n_rows, int64_t nnz_hint, int p, const double* x_full, int64_t x_row_offset,
-                               const double* z, double* y, double* r, double alpha, double beta, double gamma,
-                               double coef, double* dots, meld_stream_t stream) {
-  MELD_CHECK_ARG(rowptr && dw && x_full && y && n_rows >= 0 && p >= 1, "meld_cheby_step: bad arguments");
+extern "C" int meld_cheby_step(const meld_laplacian_t* L, int p, const double* x_full, int64_t x_row_offset, const double* z,
+                               double* y, double* r, double alpha, double beta, double gamma, double coef, double* dots,
+                               meld_stream_t stream) {
+  MELD_CHECK_ARG(laplacian_ok(L) && x_full && y && L->n_rows >= 0 && p >= 1, "meld_cheby_step: bad arguments");
   MELD_CHECK_ARG(gamma == 0.0 || z != nullptr, "meld_cheby_step: z is required when gamma != 0");
   MELD_CHECK_ARG(dots == nullptr || p == 1, "meld_cheby_step: dots are only produced for p == 1");
   hipStream_t st = S(stream);
   if (dots) MELD_HIP_CALL(hipMemsetAsync(dots, 0, sizeof(double) * 2 * DOT_SLOTS, st));
-  if (n_rows == 0) return MELD_OK;  // a rank of the row-sharded driver that owns no rows: nothing to compute, the
-                                    // partial sums stay zero and the caller still takes part in every collective
-  constexpr int RB = 32;
-  // LDS chunk: ~1.3x the mean span of RB rows, multiple of 256, within [512, 3072] entries
-  const double mean_span = (nnz_hint > 0) ? (double)nnz_hint / (double)n_rows * RB : 1024.0;
-  auto pick_chunk = [&](int P) {
-    int64_t c = (int64_t)(mean_span * 1.3) / 256 * 256 + 256;
-    const int64_t cmax = (48 * 1024) / (8 * P) / 256 * 256;
-    return (int)std::max<int64_t>(512, std::min<int64_t>(c, cmax));
-  };
+  if (L->n_rows == 0) return MELD_OK;  // a rank of the row-sharded driver that owns no rows: nothing to compute, the
+                                       // partial sums stay zero and the caller still takes part in every collective
+  if (L->layout) {
+    const int rc = pt_step(L->layout, L->rowptr, L->dw, p, x_full, x_row_offset, z, y, r, alpha, beta, gamma, coef, dots, nullptr, st);
+    if (rc != MELD_OK) return rc;
+    MELD_LAUNCH_CHECK("pt_step_kernel");
+    return MELD_OK;
+  }
   int colofs = 0;
   if (p % 2 == 0) {
-    while (colofs + 4 <= p) {
-      launch_cheby<4, RB>(rowptr, col, val, dw, n_rows, p, colofs, x_full, x_row_offset, z, y, r, alpha, beta, gamma,
-                          coef, nullptr, pick_chunk(4), st);
-      colofs += 4;
-    }
-    if (colofs + 2 <= p) {
-      launch_cheby<2, RB>(rowptr, col, val, dw, n_rows, p, colofs, x_full, x_row_offset, z, y, r, alpha, beta, gamma,
-                          coef, nullptr, pick_chunk(2), st);
-      colofs += 2;
-    }
+    for (; colofs + 4 <= p; colofs += 4)
+      launch_cheby<4>(L, p, colofs, x_full, x_row_offset, z, y, r, alpha, beta, gamma, coef, nullptr, st);
+    if (colofs + 2 <= p) launch_cheby<2>(L, p, colofs, x_full, x_row_offset, z, y, r, alpha, beta, gamma, coef, nullptr, st);
   } else {
-    for (; colofs < p; ++colofs)
-      launch_cheby<1, RB>(rowptr, col, val, dw, n_rows, p, colofs, x_full, x_row_offset, z, y, r, alpha, beta, gamma,
-                          coef, dots, pick_chunk(1), st);
+    for (; colofs < p; ++colofs) launch_cheby<1>(L, p, colofs, x_full, x_row_offset, z, y, r, alpha, beta, gamma, coef, dots, st);
   }
   MELD_LAUNCH_CHECK("cheby_step_kernel");
   return MELD_OK;
@@ -595,36 +576,61 @@ extern "C" int meld_cheby_step(const int64_t* rowptr, const int32_t* col, const 
 
 // n_iter iterations of the Lanczos recurrence of L = diag(dw) - W with every scalar on the device.
 // Replaces the per-iteration host round trips of the lmax estimate ([UPSTREAM pygsp
-// Graph.estimate_lmax], reference meld/filter.py:39): one SpMV, one wave-sized scalar kernel, one
-// axpby, one scalar kernel per iteration, nothing read back until the caller looks at alphas/betas.
-extern "C" int meld_lanczos_steps(const int64_t* rowptr, const int32_t* col, const double* val, const double* dw,
-                                  int64_t n_rows, int64_t nnz_hint, double* v0, double* v1, double* v2, double* state,
-                                  double* alphas, double* betas, int it_begin, int n_iter, double* scratch,
+// Graph.estimate_lmax], reference meld/filter.py:39): nothing is read back until the caller looks at alphas/betas.
+extern "C" int meld_lanczos_steps(const meld_laplacian_t* L, double* v0, double* v1, double* v2, double* state, double* alphas,
+                                  double* betas, int it_begin, int n_iter, double* scratch, const int32_t* stop,
                                   meld_stream_t stream) {
-  MELD_CHECK_ARG(rowptr && dw && v0 && v1 && v2 && state && alphas && betas && scratch && n_rows > 0 && it_begin >= 0 &&
+  MELD_CHECK_ARG(laplacian_ok(L) && v0 && v1 && v2 && state && alphas && betas && scratch && L->n_rows > 0 && it_begin >= 0 &&
                      n_iter >= 0,
                  "meld_lanczos_steps: bad arguments");
   hipStream_t st = S(stream);
   double* V[3] = {v0, v1, v2};
-  double* dots = scratch;                  // 2 * DOT_SLOTS, zero on entry of iteration 0 (caller) and re-zeroed by the beta kernel
-  double* nrm2 = scratch + 2 * DOT_SLOTS;  // DOT_SLOTS
-  constexpr int RB = 32;
-  const double mean_span = (nnz_hint > 0) ? (double)nnz_hint / (double)n_rows * RB : 1024.0;
-  const int chunk = (int)std::max<int64_t>(512, std::min<int64_t>((int64_t)(mean_span * 1.3) / 256 * 256 + 256, (48 * 1024) / 8 / 256 * 256));
+  const int64_t n_rows = L->n_rows;
   const unsigned grid_ax = (unsigned)std::min<int64_t>(2048, ceil_div(n_rows, 256));
+  if (!L->layout) {
+    // CSR-stream kernel: one SpMV, the alpha step fused into the axpy, one wave-sized scalar kernel per iteration
+    double* dots = scratch;                  // 2 * DOT_SLOTS, zero on entry of iteration 0 (caller) and re-zeroed by the beta kernel
+    double* nrm2 = scratch + 2 * DOT_SLOTS;  // DOT_SLOTS
+    for (int it = it_begin; it < it_begin + n_iter; ++it) {
+      // roles rotate with the iteration: u_prev = V[it % 3], u = V[(it + 1) % 3], y = V[(it + 2) % 3]
+      double* u_prev = V[it % 3];
+      double* u = V[(it + 1) % 3];
+      double* y = V[(it + 2) % 3];
+      // y = s_cur L u - beta_{k-1} s_prev u_prev ;  dots <- <y, u>
+      launch_cheby<1>(L, 1, 0, u, 0, u_prev, y, nullptr, 0.0, 0.0, 0.0, 0.0, dots, st, state);
+      // alpha_k = s_cur <y, u>;  w = y - alpha v_k (in y) ;  nrm2 <- |w|^2
+      // (the beta step stays a one-wave launch of its own: folded into the axpy behind a last-workgroup ticket it needs a
+      // __threadfence per workgroup, which on this part writes the L2 back -- measured 4.9 vs 3.6 ms per estimate)
+      hipLaunchKernelGGL(lanczos_axpy_fused_kernel, dim3(grid_ax), dim3(256), 0, st, state, dots, nrm2, alphas, it, u, y, n_rows);
+      hipLaunchKernelGGL(lanczos_beta_kernel, dim3(1), dim3(64), 0, st, state, nrm2, dots, betas, it, nrm2);
+    }
+    MELD_LAUNCH_CHECK("meld_lanczos_steps");
+    return MELD_OK;
+  }
+  // Tiled layout, two launches per iteration: the SpMV (which derives its scalars from the previous axpy's partial sums and records
+  // beta of the previous iteration, PtLanczos in common.hpp) and the axpy.  (The one-wave beta kernel that used to sit between them
+  // cost a launch and its gaps, ~7 us of ~90 per iteration; folding it into the axpy behind a last-workgroup ticket had cost more
+  // than it saved -- a device-scope release per workgroup.)  Parity buffers in scratch (8 DOT_SLOTS doubles):
+  //   dots[2][2 DOT_SLOTS] | nrm2[2][DOT_SLOTS] | st[2][8];  iteration k adds <y, u> into dots[k & 1] and |w|^2 into nrm2[k & 1].
+  double* dots_pp = scratch;
+  double* nrm2_pp = scratch + 4 * DOT_SLOTS;
+  double* st_pp = scratch + 6 * DOT_SLOTS;
+  if (it_begin == 0) hipLaunchKernelGGL(lanczos_pp_init_kernel, dim3(1), dim3(256), 0, st, state, scratch);
   for (int it = it_begin; it < it_begin + n_iter; ++it) {
-    // roles rotate with the iteration: u_prev = V[it % 3], u = V[(it + 1) % 3], y = V[(it + 2) % 3]
     double* u_prev = V[it % 3];
     double* u = V[(it + 1) % 3];
     double* y = V[(it + 2) % 3];
-    // y = s_cur L u - beta_{k-1} s_prev u_prev ;  dots <- <y, u>
-    launch_cheby<1, RB>(rowptr, col, val, dw, n_rows, 1, 0, u, 0, u_prev, y, nullptr, 0.0, 0.0, 0.0, 0.0, dots, chunk, st,
-                        state);
-    // alpha_k = s_cur <y, u>;  w = y - alpha v_k (in y) ;  nrm2 <- |w|^2
-    // (the beta step stays a one-wave launch of its own: folded into the axpy behind a last-workgroup ticket it needs a
-    // __threadfence per workgroup, which on this part writes the L2 back -- measured 4.9 vs 3.6 ms per estimate)
-    hipLaunchKernelGGL(lanczos_axpy_fused_kernel, dim3(grid_ax), dim3(256), 0, st, state, dots, nrm2, alphas, it, u, y, n_rows);
-    hipLaunchKernelGGL(lanczos_beta_kernel, dim3(1), dim3(64), 0, st, state, nrm2, dots, betas, it, nrm2);
+    const int cur = it & 1, prv = cur ^ 1;
+    PtLanczos lz{nrm2_pp + prv * DOT_SLOTS, nrm2_pp + cur * DOT_SLOTS, st_pp + prv * 8, st_pp + cur * 8, betas, it, stop};
+    const int rc = pt_step(L->layout, L->rowptr, L->dw, 1, u, 0, u_prev, y, nullptr, 0.0, 0.0, 0.0, 0.0, dots_pp + cur * 2 * DOT_SLOTS,
+                           nullptr, st, 0.0, &lz);
+    if (rc != MELD_OK) return rc;
+    hipLaunchKernelGGL(lanczos_axpy_pp_kernel, dim3(grid_ax), dim3(256), 0, st, st_pp + cur * 8, dots_pp + cur * 2 * DOT_SLOTS,
+                       nrm2_pp + cur * DOT_SLOTS, dots_pp + prv * 2 * DOT_SLOTS, alphas, it, u, y, n_rows, stop);
+  }
+  if (n_iter > 0) {
+    const int last = it_begin + n_iter - 1;
+    hipLaunchKernelGGL(lanczos_pp_last_beta_kernel, dim3(1), dim3(64), 0, st, nrm2_pp + (last & 1) * DOT_SLOTS, betas, last, stop);
   }
   MELD_LAUNCH_CHECK("meld_lanczos_steps");
   return MELD_OK;
@@ -634,68 +640,18 @@ extern "C" int meld_lanczos_steps(const int64_t* rowptr, const int32_t* col, con
 // driver: it interleaves them with the all-reduces of the partial sums (dots after the SpMV, nrm2 after the
 // axpy) and the all-gather of the new vector, all stream-ordered, so that a sharded iteration needs no host
 // round trip either.  x_full [n_total] is the gathered iterate, the other vectors are the local rows.
-extern "C" int meld_lanczos_spmv(const int64_t* rowptr, const int32_t* col, const double* val, const double* dw,
-                                 int64_t n_rows, int64_t nnz_hint, const double* x_full, int64_t x_row_offset,
-                                 const double* z_local, double* y_local, const double* state, double* dots,
-                                 meld_stream_t stream) {
-  MELD_CHECK_ARG(rowptr && dw && x_full && z_local && y_local && state && dots && n_rows >= 0, "meld_lanczos_spmv: bad arguments");
-  if (n_rows == 0) return MELD_OK;  // empty shard (the beta phase has zeroed the partial sums)
-  constexpr int RB = 32;
-  const double mean_span = (nnz_hint > 0) ? (double)nnz_hint / (double)n_rows * RB : 1024.0;
-  const int chunk = (int)std::max<int64_t>(512, std::min<int64_t>((int64_t)(mean_span * 1.3) / 256 * 256 + 256, (48 * 1024) / 8 / 256 * 256));
-  launch_cheby<1, RB>(rowptr, col, val, dw, n_rows, 1, 0, x_full, x_row_offset, z_local, y_local, nullptr, 0.0, 0.0, 0.0, 0.0,
-                      dots, chunk, S(stream), state);
-  MELD_LAUNCH_CHECK("meld_lanczos_spmv");
-  return MELD_OK;
-}
-// The same two drivers on the panel-tiled layout (spmm_tiled.hip).
-extern "C" int meld_pt_lanczos_steps(const meld_pt_layout_t* layout, const int64_t* rowptr, const double* dw, int64_t n_rows,
-                                     double* v0, double* v1, double* v2, double* state, double* alphas, double* betas,
-                                     int it_begin, int n_iter, double* scratch, const int32_t* stop, meld_stream_t stream) {
-  MELD_CHECK_ARG(layout && rowptr && dw && v0 && v1 && v2 && state && alphas && betas && scratch && n_rows > 0 &&
-                     it_begin >= 0 && n_iter >= 0,
-                 "meld_pt_lanczos_steps: bad arguments");
-  hipStream_t st = S(stream);
-  double* V[3] = {v0, v1, v2};
-  // Two launches per iteration: the SpMV (which derives its scalars from the previous axpy's partial sums and records beta of the
-  // previous iteration, PtLanczos in common.hpp) and the axpy.  (The one-wave beta kernel that used to sit between them cost a
-  // launch and its gaps, ~7 us of ~90 per iteration; folding it into the axpy behind a last-workgroup ticket had cost more than
-  // it saved -- a device-scope release per workgroup.)  Parity buffers in scratch (8 DOT_SLOTS doubles):
-  //   dots[2][2 DOT_SLOTS] | nrm2[2][DOT_SLOTS] | st[2][8];  iteration k adds <y, u> into dots[k & 1] and |w|^2 into nrm2[k & 1].
-  double* dots_pp = scratch;
-  double* nrm2_pp = scratch + 4 * DOT_SLOTS;
-  double* st_pp = scratch + 6 * DOT_SLOTS;
-  if (it_begin == 0) hipLaunchKernelGGL(lanczos_pp_init_kernel, dim3(1), dim3(256), 0, st, state, scratch);
-  const unsigned grid_ax = (unsigned)std::min<int64_t>(2048, ceil_div(n_rows, 256));
-  for (int it = it_begin; it < it_begin + n_iter; ++it) {
-    double* u_prev = V[it % 3];
-    double* u = V[(it + 1) % 3];
-    double* y = V[(it + 2) % 3];
-    const int cur = it & 1, prv = cur ^ 1;
-    PtLanczos lz{nrm2_pp + prv * DOT_SLOTS, nrm2_pp + cur * DOT_SLOTS, st_pp + prv * 8, st_pp + cur * 8, betas, it, stop};
-    const int rc = pt_step(layout, rowptr, dw, 1, u, 0, u_prev, y, nullptr, 0.0, 0.0, 0.0, 0.0, dots_pp + cur * 2 * DOT_SLOTS, nullptr, st, 0.0, &lz);
+extern "C" int meld_lanczos_spmv(const meld_laplacian_t* L, const double* x_full, int64_t x_row_offset, const double* z_local,
+                                 double* y_local, const double* state, double* dots, meld_stream_t stream) {
+  MELD_CHECK_ARG(laplacian_ok(L) && x_full && z_local && y_local && state && dots && L->n_rows >= 0, "meld_lanczos_spmv: bad arguments");
+  if (L->n_rows == 0) return MELD_OK;  // empty shard (the beta phase has zeroed the partial sums)
+  if (L->layout) {
+    const int rc = pt_step(L->layout, L->rowptr, L->dw, 1, x_full, x_row_offset, z_local, y_local, nullptr, 0.0, 0.0, 0.0, 0.0, dots,
+                           state, S(stream));
     if (rc != MELD_OK) return rc;
-    hipLaunchKernelGGL(lanczos_axpy_pp_kernel, dim3(grid_ax), dim3(256), 0, st, st_pp + cur * 8, dots_pp + cur * 2 * DOT_SLOTS,
-                       nrm2_pp + cur * DOT_SLOTS, dots_pp + prv * 2 * DOT_SLOTS, alphas, it, u, y, n_rows, stop);
+  } else {
+    launch_cheby<1>(L, 1, 0, x_full, x_row_offset, z_local, y_local, nullptr, 0.0, 0.0, 0.0, 0.0, dots, S(stream), state);
   }
-  if (n_iter > 0) {
-    const int last = it_begin + n_iter - 1;
-    hipLaunchKernelGGL(lanczos_pp_last_beta_kernel, dim3(1), dim3(64), 0, st, nrm2_pp + (last & 1) * DOT_SLOTS, betas, last, stop);
-  }
-  MELD_LAUNCH_CHECK("meld_pt_lanczos_steps");
-  return MELD_OK;
-}
-
-extern "C" int meld_pt_lanczos_spmv(const meld_pt_layout_t* layout, const int64_t* rowptr, const double* dw, int64_t n_rows,
-                                    const double* x_full, int64_t x_row_offset, const double* z_local, double* y_local,
-                                    const double* state, double* dots, meld_stream_t stream) {
-  MELD_CHECK_ARG(layout && rowptr && dw && x_full && z_local && y_local && state && dots && n_rows >= 0,
-                 "meld_pt_lanczos_spmv: bad arguments");
-  if (n_rows == 0) return MELD_OK;
-  const int rc = pt_step(layout, rowptr, dw, 1, x_full, x_row_offset, z_local, y_local, nullptr, 0.0, 0.0, 0.0, 0.0, dots,
-                         state, S(stream));
-  if (rc != MELD_OK) return rc;
-  MELD_LAUNCH_CHECK("meld_pt_lanczos_spmv");
+  MELD_LAUNCH_CHECK("meld_lanczos_spmv");
   return MELD_OK;
 }
 extern "C" int meld_lanczos_alpha(double* state, const double* dots, double* nrm2, double* alphas, int it,

@@ -94,11 +94,9 @@ struct StepArgs {
   PtLanczos lz;  // (lz.nrm2_prev != NULL: the scalars are derived in the kernel, see common.hpp)
   int64_t x_row_offset;
   double alpha, beta, gamma, coef;
-  double coef_x;  // r += coef * y + coef_x * x (own rows): lets a recurrence touch r every other step (meld_pt_cheby_run)
+  double coef_x;  // r += coef * y + coef_x * x (own rows): lets a recurrence touch r every other step (meld_cheby_run)
   int nb;
   int ld, colofs;
-  unsigned long long* stamps;  // development: [nb][16][8] wall-clock stamps of every wave (meld_pt_debug_stamps), or NULL
-  int ablate;  // timing-only modes (results wrong): 4 no panel loads, 8 panel gathers from a 16 KB window of x
 };
 
 template <int P>
@@ -233,11 +231,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(48))) void 
     alpha = a.coef_dev[3];
     gamma = a.coef_dev[4];
   }
-  const int ab = a.ablate;
-  auto stamp = [&](int i) __attribute__((always_inline)) {
-    if (a.stamps != nullptr && lane == 0) a.stamps[((size_t)b * 16 + w) * 8 + i] = wall_clock64();
-  };
-  stamp(0);
   // the block's header words (one scalar load instead of a chain of dependent ones: first row, rows, tiles, distinct
   // OUT columns, CSR offset of the first row) sit behind the symmetry sum in the block's last segment row
   const int32_t* segb = a.seg + (size_t)b * SEGROWS * SEGW;
@@ -261,17 +254,14 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(48))) void 
   // register with a load in flight must never be copied and the allocator copies asm operands freely.  Loads return
   // in order and every slot is re-issued right after it has been read, so when chunk k is wanted exactly 2 (U - 1)
   // younger loads are in flight: s_waitcnt vmcnt(14).  Past the end of a wave's stream the loads read the next
-  // wave's entries or the slack behind the arrays; nothing is done with them.
-#ifndef PT_NT
-#define PT_NT " nt"
-#endif
+  // wave's entries or the slack behind the arrays; nothing is done with them.  The stream is read once: "nt" loads.
 #define PT_SLOT_LOAD(VLO, VHI, IX)                                                                          \
-  asm volatile("global_load_dwordx2 v[" #VLO ":" #VHI "], %0, %2" PT_NT "\n\tglobal_load_dword v" #IX ", %1, %3" PT_NT \
+  asm volatile("global_load_dwordx2 v[" #VLO ":" #VHI "], %0, %2 nt\n\tglobal_load_dword v" #IX ", %1, %3 nt" \
                :                                                                                            \
                : "v"(off8), "v"(off4), "s"(pvk), "s"(pik)                                                   \
                : "memory", "v" #VLO, "v" #VHI, "v" #IX)
 #define PT_SLOT_LOAD32(VLO, VHI, IX)                                                                   \
-  asm volatile("global_load_dword v" #VLO ", %0, %1" PT_NT "\n\tglobal_load_dword v" #IX ", %0, %2" PT_NT        \
+  asm volatile("global_load_dword v" #VLO ", %0, %1 nt\n\tglobal_load_dword v" #IX ", %0, %2 nt"       \
                :                                                                                         \
                : "v"(off4), "s"(pvk32), "s"(pik)                                                         \
                : "memory", "v" #VLO, "v" #VHI, "v" #IX)
@@ -369,14 +359,17 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(48))) void 
     s_cons[tid] = 0;
   }
   if (tid == 0) s_in_done = 0;
-  stamp(1);
   __syncthreads();
-  stamp(2);
 
   // No workgroup barrier from here to the end of the block's tiles: a consumer wave waits only for the loaders
   // (tile t staged), the loaders only for the slowest consumer NB tiles back (and once for the end of the IN part).
   if (w < NW) {
     // ------------------------------------------------------------------ consumer wave
+    // vmcnt(0), said with the builtin so that hipcc's wait-count pass hears it: nothing this wave has asked for is pending
+    // (the staging loop above has waited for its loads, and with them for the first U chunks).  Without it the pass merges
+    // this path with the loader waves' and guards the loop's LDS updates against THEIR gathers -- s_waitcnt vmcnt(10) in
+    // the stream loop, four loads fewer in flight than the hand-counted vmcnt(14) keeps.
+    __builtin_amdgcn_s_waitcnt(0x0F70);
     int cur = -1;                // the tile this wave holds (tiles are entered in order, every one exactly once)
     bool in_open = true;         // the IN part has not been signed off yet
     double s0 = 0.0, s1 = 0.0;   // running sums of the lane's current row run
@@ -384,7 +377,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(48))) void 
       PT_WAIT_LDS();  // my reads of the block's own slice have completed
       if (lane == 0) lds_bump(&s_in_done);
       in_open = false;
-      stamp(3);
     };
     // Two-stage pipeline over the chunks: the x values of chunk k are requested from LDS at the end of step k and
     // consumed at step k + 1 (after the entry wait of chunk k + 1), so the LDS round trip is covered by a step.
@@ -458,7 +450,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(48))) void 
       dB = dC;
     }
     stage2();
-    stamp(4);
     // the slots still have loads in flight (re-issues past the end of the stream)
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (in_open) finish_in();
@@ -482,9 +473,9 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(48))) void 
     };
     auto gather = [&]() __attribute__((always_inline)) {
 #pragma unroll
-      for (int k = 0; k < PER; ++k) xv[k] = ldg<P>(xs, (ab & 8) ? (col[k] & 1023) : col[k], a.ld, a.colofs);
+      for (int k = 0; k < PER; ++k) xv[k] = ldg<P>(xs, col[k], a.ld, a.colofs);
     };
-    if (lw < T && !(ab & 4)) {
+    if (lw < T) {
       load_list(lw);
       gather();
       if (lw + NL < T) load_list(lw + NL);
@@ -497,12 +488,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(48))) void 
       } else {        // the ring overlays the block's own slice: every consumer has finished the IN part
         while (lds_peek(&s_in_done) < NW) __builtin_amdgcn_s_sleep(1);
       }
-      if (!(ab & 4)) {
 #pragma unroll
-        for (int k = 0; k < PER; ++k) lds_put<P>(lds, XBASE + (unsigned)(buf * CP + k * 64 + lane) * STRIDE, xv[k]);
-        if (t + NL < T) gather();                   // my next tile (its list landed one tile ago)
-        if (t + 2 * NL < T) load_list(t + 2 * NL);  // and the list of the one after
-      }
+      for (int k = 0; k < PER; ++k) lds_put<P>(lds, XBASE + (unsigned)(buf * CP + k * 64 + lane) * STRIDE, xv[k]);
+      if (t + NL < T) gather();                   // my next tile (its list landed one tile ago)
+      if (t + 2 * NL < T) load_list(t + 2 * NL);  // and the list of the one after
       PT_WAIT_LDS();  // the panel has landed
       if (lane == 0) lds_bump(&s_prod[buf]);
     }
@@ -530,10 +519,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(48))) void 
     if (gamma != 0.0 || lz_on) zl[q] = ldg<P>(zs, row, a.ld, a.colofs);
     if (a.r != nullptr) rl_[q] = ldg<P>(a.r, row, a.ld, a.colofs);
   }
-  stamp(5);
   PT_WAIT_LDS();
   __builtin_amdgcn_s_barrier();  // every accumulator is final
-  stamp(6);
   if (lz_on) {  // every wave derives the iteration's scalars from the same 64 partial sums (same order, same value)
     const double beta_prev = sqrt(wave_sum(lz_part));
     const double s_prev = a.lz.state_prev[0];
@@ -565,7 +552,6 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_num_vgpr(48))) void 
       if (a.r != nullptr) stg<P>(a.r, row, a.ld, a.colofs, rl_[q]);
     }
   }
-  stamp(7);
   if (a.dots != nullptr) {
     d_yx = wave_sum(d_yx);
     d_yy = wave_sum(d_yy);
@@ -1249,23 +1235,6 @@ __global__ __launch_bounds__(256) void pt_round_f32_kernel(const double* __restr
 
 using namespace meld;
 
-static int g_pt_ablate = 0;
-// timing-only ablations for tools/spmm_compare.py (results are wrong while set): 4 no panel loads, 8 panel gathers
-// from a 16 KB window of x
-extern "C" int meld_pt_debug_ablate(int mask) {
-  g_pt_ablate = mask;
-  return MELD_OK;
-}
-
-static unsigned long long* g_pt_stamps = nullptr;
-// development: every wave of the following step launches writes 8 wall-clock stamps (100 MHz) to buf[nb][16][8]
-// (0 start, 1 before / 2 after the opening barrier, 3 IN part done, 4 stream done, 5 before / 6 after the closing
-// barrier, 7 results written); NULL switches it off
-extern "C" int meld_pt_debug_stamps(unsigned long long* buf) {
-  g_pt_stamps = buf;
-  return MELD_OK;
-}
-
 extern "C" int meld_pt_geometry(int* consumer_waves, int* rows_max, int* tile_cols, int* tiles_max) {
   if (consumer_waves) *consumer_waves = pt::NW;
   if (rows_max) *rows_max = pt::RMAX;
@@ -1397,70 +1366,8 @@ int meld::pt_step(const meld_pt_layout_t* L, const int64_t* rowptr, const double
   a.list_cols = L->list_cols; a.pval = L->pval; a.pidx = L->pidx; a.cdesc = L->cdesc; a.rowptr = rowptr; a.dw = dw; a.x_full = x_full;
   a.z = z; a.y = y; a.r = r; a.dots = dots; a.coef_dev = coef_dev; a.x_row_offset = x_row_offset; a.alpha = alpha;
   a.beta = beta; a.gamma = gamma; a.coef = coef; a.coef_x = coef_x; a.nb = L->nb; a.ld = p; a.colofs = 0;
-  a.ablate = g_pt_ablate;
-  a.stamps = g_pt_stamps;
   a.pval32 = L->pval32;
   if (lz != nullptr) a.lz = *lz; else a.lz = PtLanczos{nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr};
   // the fp32 copy of the values serves the lmax estimate only (p = 1 with device-resident Lanczos scalars)
   return pt_step_cols(a, p, st, (coef_dev != nullptr || lz != nullptr) && p == 1 && L->pval32 != nullptr);
-}
-
-extern "C" int meld_pt_cheby_step(const meld_pt_layout_t* layout, const int64_t* rowptr, const double* dw, int64_t n_rows,
-                                  int p, const double* x_full, int64_t x_row_offset, const double* z, double* y, double* r,
-                                  double alpha, double beta, double gamma, double coef, double* dots, meld_stream_t stream) {
-  MELD_CHECK_ARG(layout && layout->blk_row && layout->blk_ntile && layout->blk_ndist && layout->seg && layout->list_cols &&
-                     layout->pval && layout->pidx && rowptr && dw && x_full && y && n_rows >= 0 && p >= 1,
-                 "meld_pt_cheby_step: bad arguments");
-  MELD_CHECK_ARG(gamma == 0.0 || z != nullptr, "meld_pt_cheby_step: z is required when gamma != 0");
-  MELD_CHECK_ARG(dots == nullptr || p == 1, "meld_pt_cheby_step: dots are only produced for p == 1");
-  hipStream_t st = S(stream);
-  if (dots) MELD_HIP_CALL(hipMemsetAsync(dots, 0, sizeof(double) * 2 * pt::DOT_SLOTS, st));
-  if (n_rows == 0) return MELD_OK;
-  const int rc = pt_step(layout, rowptr, dw, p, x_full, x_row_offset, z, y, r, alpha, beta, gamma, coef, dots, nullptr, st);
-  if (rc != MELD_OK) return rc;
-  MELD_LAUNCH_CHECK("pt_step_kernel");
-  return MELD_OK;
-}
-
-// Steps k = 2 .. n_coef - 1 of the Chebyshev recurrence in one call (single GPU: x_row_offset = 0, no collective between
-// the steps):  T_k = alpha2 L T_{k-1} + beta2 T_{k-1} - T_{k-2},  r += c_k T_k  [UPSTREAM pygsp cheby_op, reference
-// meld/filter.py:59].  t_prev2 / t_prev1 hold T_0 / T_1 on entry and are used as the two ping-pong buffers (T_k
-// overwrites T_{k-2}); r already holds c_0 / 2 T_0 + c_1 T_1.  The accumulator is touched every OTHER step only: a step
-// that holds T_k in its result and T_{k-1} in its own rows of the iterate adds c_k T_k + c_{k-1} T_{k-1} at once, the
-// step before it neither reads nor writes r -- 32 of the 80 bytes of vector traffic per row and step pair at p = 2.
-// coeffs: n_coef doubles on the HOST.  *last = 0 / 1: the buffer (t_prev2 / t_prev1) that holds T of the last order.
-extern "C" int meld_pt_cheby_run(const meld_pt_layout_t* layout, const int64_t* rowptr, const double* dw, int64_t n_rows, int p,
-                                 double* t_prev2, double* t_prev1, double* r, const double* coeffs, int n_coef, double alpha2,
-                                 double beta2, int* last, meld_stream_t stream) {
-  MELD_CHECK_ARG(layout && layout->blk_row && layout->blk_ntile && layout->blk_ndist && layout->seg && layout->list_cols &&
-                     layout->pval && layout->pidx && rowptr && dw && t_prev2 && t_prev1 && r && coeffs && n_rows >= 0 && p >= 1 &&
-                     n_coef >= 2,
-                 "meld_pt_cheby_run: bad arguments");
-  hipStream_t st = S(stream);
-  double* t_old = t_prev2;
-  double* t_cur = t_prev1;
-  int which = 1;  // t_cur is t_prev1
-  if (n_rows > 0) {
-    int k = 2;
-    if ((n_coef - 2) % 2 == 1) {  // an odd number of steps: the first one alone
-      const int rc = pt_step(layout, rowptr, dw, p, t_cur, 0, t_old, t_old, r, alpha2, beta2, -1.0, coeffs[k], nullptr, nullptr, st, 0.0);
-      if (rc != MELD_OK) return rc;
-      std::swap(t_old, t_cur);
-      which ^= 1;
-      ++k;
-    }
-    for (; k + 1 < n_coef; k += 2) {
-      // T_k: no accumulator traffic
-      int rc = pt_step(layout, rowptr, dw, p, t_cur, 0, t_old, t_old, nullptr, alpha2, beta2, -1.0, 0.0, nullptr, nullptr, st, 0.0);
-      if (rc != MELD_OK) return rc;
-      std::swap(t_old, t_cur);
-      // T_{k+1}, and r += c_{k+1} T_{k+1} + c_k T_k (T_k = this step's own rows of the iterate)
-      rc = pt_step(layout, rowptr, dw, p, t_cur, 0, t_old, t_old, r, alpha2, beta2, -1.0, coeffs[k + 1], nullptr, nullptr, st, coeffs[k]);
-      if (rc != MELD_OK) return rc;
-      std::swap(t_old, t_cur);
-    }
-  }
-  if (last) *last = which;
-  MELD_LAUNCH_CHECK("pt_step_kernel");
-  return MELD_OK;
 }

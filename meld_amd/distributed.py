@@ -47,7 +47,7 @@ class Comm:
 
     def rccl(self):
         """Handle of the library's own RCCL communicator over this group (``meld_rccl_comm_create``), for the C-side recurrence
-        loops (``meld_cheby_run_sharded`` / ``meld_lanczos_steps_sharded``: kernel and collective of every step enqueued from
+        loops (``meld_cheby_run`` / ``meld_lanczos_steps_sharded``: kernel and collective of every step enqueued from
         one call), or None when the group does not run on RCCL (gloo, the host-staged test collectives) or the loops are
         switched off (``MELD_SHARDED_C_LOOPS=0``).  The unique id travels through torch.distributed.  Created once per process
         group (ncclCommInitRank is a collective); the cache entry holds the group OBJECT, so a group torn down and re-created --

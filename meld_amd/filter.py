@@ -218,7 +218,7 @@ def chebyshev_apply(G, signal, coeffs, lmax):
     with _EventSpan("cheby_steps", steps=int(c.shape[0] - 2), N=G.N, p=p, nnz=G.nnz):
         if comm is None and c.shape[0] > 2 and hasattr(ops, "cheby_run") and opt("MELD_CHEBY_RUN", "1") != "0" \
                 and ops.cheby_run(G, p, t_old, t_cur, r, c, 2.0 / a1, -2.0 * a2 / a1):
-            return r  # (one call for all the steps; r is read and written every other step only)
+            return r  # (one call for all the steps; on the tiled layout r is read and written every other step only)
         if comm is not None and c.shape[0] > 2 and hasattr(ops, "cheby_run_sharded") and opt("MELD_CHEBY_RUN", "1") != "0" \
                 and ops.cheby_run_sharded(G, p, t_old, t_cur, r, c, 2.0 / a1, -2.0 * a2 / a1) is not None:
             return r  # (row shard on RCCL: kernel + all-gather of every step enqueued from one C call)
@@ -333,7 +333,7 @@ def _lanczos_lmax_device(G, ops, u0, tol, max_iter, check_every):
     travel to the host on a side stream while the NEXT batch already runs: the convergence check (a k x k tridiagonal
     eigenproblem on the host) overlaps with device work instead of idling the GPU once per batch (12 idle gaps of ~0.1 ms at
     500k cells, 75 iterations).  Once the check has passed, a flag set from the side stream voids what is left of the batch in
-    flight (its launches return at once, ``stop`` of ``meld_pt_lanczos_steps``), so the overlap costs an iteration or two of
+    flight (its launches return at once, ``stop`` of ``meld_lanczos_steps`` on the tiled layout), so the overlap costs an iteration or two of
     wasted work, not a batch (``MELD_LANCZOS_SPECULATE=0``: the serial loop)."""
     dev, n = G.val.device, G.N
     slots = ops.dot_slots()

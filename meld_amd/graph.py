@@ -1363,22 +1363,27 @@ class HipOps:
         G.info["spmm"] = "tiled"
         return G.pt
 
-    def cheby_step(self, G, p, x_full, x_row_off, z, y, r, alpha, beta, gamma, coef, dots=None):
-        pt = self.pt_layout(G)
-        if pt is not None:
-            import ctypes as C
+    def _operator(self, G, decide=True):
+        """``G``'s ``meld_laplacian_t`` by reference, as every recurrence entry takes it: built once per graph and kept on it
+        beside ``G.pt`` (and again when the layout is); ``layout`` is NULL where ``pt_layout`` keeps the graph on the
+        CSR-stream kernel.  The record holds addresses only -- ``G`` keeps the tensors and the ``PtLayout`` alive.
+        ``decide=False`` (an entry that reads the CSR arrays whatever the layout) does not have a layout built for its sake."""
+        import ctypes as C
 
-            check(
-                self.lib.meld_pt_cheby_step(C.byref(pt["struct"]), ptr(G.rowptr), ptr(G.dw_dev), G.n_rows, p, ptr(x_full), x_row_off,
-                                            ptr(z), ptr(y), ptr(r), float(alpha), float(beta), float(gamma), float(coef),
-                                            ptr(dots), _stream()),
-                "meld_pt_cheby_step",
-            )
-            return
+        pt = self.pt_layout(G) if decide or getattr(G, "pt", None) is not None else None
+        kept = getattr(G, "operator", None)
+        if kept is None or kept[0] is not pt:
+            from ._lib import Laplacian
+
+            rec = Laplacian(G.rowptr.data_ptr(), G.col.data_ptr(), G.val.data_ptr(), G.dw_dev.data_ptr(), G.n_rows, G.nnz,
+                            C.pointer(pt["struct"]) if pt is not None else None)
+            G.operator = kept = (pt, rec)
+        return C.byref(kept[1])
+
+    def cheby_step(self, G, p, x_full, x_row_off, z, y, r, alpha, beta, gamma, coef, dots=None):
         check(
-            self.lib.meld_cheby_step(ptr(G.rowptr), ptr(G.col), ptr(G.val), ptr(G.dw_dev), G.n_rows, G.nnz, p, ptr(x_full),
-                                     x_row_off, ptr(z), ptr(y), ptr(r), float(alpha), float(beta), float(gamma),
-                                     float(coef), ptr(dots), _stream()),
+            self.lib.meld_cheby_step(self._operator(G), p, ptr(x_full), x_row_off, ptr(z), ptr(y), ptr(r), float(alpha), float(beta),
+                                     float(gamma), float(coef), ptr(dots), _stream()),
             "meld_cheby_step",
         )
 
@@ -1386,26 +1391,10 @@ class HipOps:
         """One recurrence step on a wide row-major signal [rows, p], 1 <= p <= 64 (``meld_cheby_step_wide``: lanes = columns, the
         matrix streamed once for all columns)."""
         check(
-            self.lib.meld_cheby_step_wide(ptr(G.rowptr), ptr(G.col), ptr(G.val), ptr(G.dw_dev), G.n_rows, int(p), ptr(x_full), int(x_row_off),
-                                          ptr(z), ptr(y), float(alpha), float(beta), float(gamma), _stream()),
+            self.lib.meld_cheby_step_wide(self._operator(G, decide=False), int(p), ptr(x_full), int(x_row_off), ptr(z), ptr(y), float(alpha),
+                                          float(beta), float(gamma), _stream()),
             "meld_cheby_step_wide",
         )
-
-    def cheby_run(self, G, p, t_prev2, t_prev1, r, coeffs, alpha2, beta2):
-        """Steps 2 .. len(coeffs) - 1 of the Chebyshev recurrence in one call (``meld_pt_cheby_run``: single GPU, tiled layout;
-        the accumulator is touched every other step).  Returns False when the graph has no tiled layout (the caller steps)."""
-        pt = self.pt_layout(G)
-        if pt is None or getattr(G, "comm", None) is not None or G.row_begin != 0:
-            return False
-        import ctypes as C
-
-        c = np.ascontiguousarray(coeffs, dtype=np.float64)
-        check(
-            self.lib.meld_pt_cheby_run(C.byref(pt["struct"]), ptr(G.rowptr), ptr(G.dw_dev), G.n_rows, p, ptr(t_prev2), ptr(t_prev1), ptr(r),
-                                       c.ctypes.data_as(C.c_void_p), int(c.shape[0]), float(alpha2), float(beta2), None, _stream()),
-            "meld_pt_cheby_run",
-        )
-        return True
 
     @staticmethod
     def _slice_begin(G, comm):
@@ -1415,27 +1404,39 @@ class HipOps:
         assert G.n_rows == 0 or begin == G.row_begin, (begin, G.row_begin)
         return begin
 
+    def _cheby_run(self, G, handle, row_begin, p, t_prev2, t_prev1, r, coeffs, alpha2, beta2):
+        """``meld_cheby_run``: steps 2 .. len(coeffs) - 1 enqueued from one C call, with the all-gather of every new slice on the
+        RCCL communicator ``handle`` (None: a single GPU).  Returns 1 / 0: whether ``t_prev1`` / ``t_prev2`` holds the last T."""
+        import ctypes as C
+
+        c = np.ascontiguousarray(coeffs, dtype=np.float64)
+        last = C.c_int(1)
+        check(
+            self.lib.meld_cheby_run(handle, self._operator(G), G.rows_pad, row_begin, p, ptr(t_prev2), ptr(t_prev1), ptr(r),
+                                    c.ctypes.data_as(C.c_void_p), int(c.shape[0]), float(alpha2), float(beta2), C.byref(last), _stream()),
+            "meld_cheby_run",
+        )
+        return int(last.value)
+
+    def cheby_run(self, G, p, t_prev2, t_prev1, r, coeffs, alpha2, beta2):
+        """Steps 2 .. len(coeffs) - 1 of the Chebyshev recurrence on a single GPU in one call (on the tiled layout the
+        accumulator is touched every other step; on the CSR-stream kernel the launches are those of stepping from Python).
+        Returns False for a graph that is a row shard (the caller steps)."""
+        if getattr(G, "comm", None) is not None or G.row_begin != 0:
+            return False
+        self._cheby_run(G, None, 0, p, t_prev2, t_prev1, r, coeffs, alpha2, beta2)
+        return True
+
     def cheby_run_sharded(self, G, p, t_prev2, t_prev1, r, coeffs, alpha2, beta2):
-        """Steps 2 .. len(coeffs) - 1 on a row shard in one call (``meld_cheby_run_sharded``: the local rows' kernel and the
-        all-gather of the new slice enqueued back to back from C on the library's own RCCL communicator).  Returns None when
-        the graph's communicator offers no RCCL handle (gloo, host-staged test collectives: the caller steps from Python),
-        else 1 / 0: whether ``t_prev1`` / ``t_prev2`` holds the last T."""
+        """The same on a row shard: the local rows' kernel and the all-gather of the new slice enqueued back to back from C on
+        the library's own RCCL communicator.  Returns None when the graph's communicator offers no RCCL handle (gloo,
+        host-staged test collectives: the caller steps from Python), else 1 / 0: whether ``t_prev1`` / ``t_prev2`` holds the
+        last T."""
         comm = getattr(G, "comm", None)
         handle = comm.rccl() if comm is not None and hasattr(comm, "rccl") else None
         if handle is None:
             return None
-        import ctypes as C
-
-        pt = self.pt_layout(G)
-        c = np.ascontiguousarray(coeffs, dtype=np.float64)
-        last = C.c_int(1)
-        check(
-            self.lib.meld_cheby_run_sharded(handle, C.byref(pt["struct"]) if pt is not None else None, ptr(G.rowptr), ptr(G.col), ptr(G.val),
-                                            ptr(G.dw_dev), G.n_rows, G.nnz, G.rows_pad, self._slice_begin(G, comm), p, ptr(t_prev2), ptr(t_prev1), ptr(r),
-                                            c.ctypes.data_as(C.c_void_p), int(c.shape[0]), float(alpha2), float(beta2), C.byref(last), _stream()),
-            "meld_cheby_run_sharded",
-        )
-        return int(last.value)
+        return self._cheby_run(G, handle, self._slice_begin(G, comm), p, t_prev2, t_prev1, r, coeffs, alpha2, beta2)
 
     def lanczos_steps_sharded(self, G, V, state, acc, alphas, betas, it_begin, n_iter):
         """Iterations of the one-reduction Lanczos recurrence on a row shard in one call (``meld_lanczos_steps_sharded``); False
@@ -1444,13 +1445,10 @@ class HipOps:
         handle = comm.rccl() if comm is not None and hasattr(comm, "rccl") else None
         if handle is None:
             return False
-        import ctypes as C
-
-        pt = self.pt_layout(G)
         check(
-            self.lib.meld_lanczos_steps_sharded(handle, C.byref(pt["struct"]) if pt is not None else None, ptr(G.rowptr), ptr(G.col), ptr(G.val),
-                                                ptr(G.dw_dev), G.n_rows, G.nnz, G.rows_pad, self._slice_begin(G, comm), ptr(V[0]), ptr(V[1]), ptr(V[2]),
-                                                ptr(state), ptr(acc), ptr(alphas), ptr(betas), int(it_begin), int(n_iter), _stream()),
+            self.lib.meld_lanczos_steps_sharded(handle, self._operator(G), G.rows_pad, self._slice_begin(G, comm), ptr(V[0]), ptr(V[1]),
+                                                ptr(V[2]), ptr(state), ptr(acc), ptr(alphas), ptr(betas), int(it_begin), int(n_iter),
+                                                _stream()),
             "meld_lanczos_steps_sharded",
         )
         return True
@@ -1459,34 +1457,16 @@ class HipOps:
         """Iterations [it_begin, it_begin + n_iter) of the device-resident Lanczos recurrence
         (``meld_lanczos_steps``): V is a [3, N] buffer of rotating vectors.  ``stop`` (int32 device tensor, optional): a launch
         that finds it nonzero does nothing (tiled layout only; the CSR kernels of small graphs run their batch out)."""
-        pt = self.pt_layout(G)
-        if pt is not None:
-            import ctypes as C
-
-            check(
-                self.lib.meld_pt_lanczos_steps(C.byref(pt["struct"]), ptr(G.rowptr), ptr(G.dw_dev), G.n_rows, ptr(V[0]), ptr(V[1]),
-                                               ptr(V[2]), ptr(state), ptr(alphas), ptr(betas), int(it_begin), int(n_iter),
-                                               ptr(scratch), ptr(stop) if stop is not None else None, _stream()),
-                "meld_pt_lanczos_steps",
-            )
-            return
         check(
-            self.lib.meld_lanczos_steps(ptr(G.rowptr), ptr(G.col), ptr(G.val), ptr(G.dw_dev), G.n_rows, G.nnz, ptr(V[0]), ptr(V[1]),
-                                        ptr(V[2]), ptr(state), ptr(alphas), ptr(betas), int(it_begin), int(n_iter), ptr(scratch), _stream()),
+            self.lib.meld_lanczos_steps(self._operator(G), ptr(V[0]), ptr(V[1]), ptr(V[2]), ptr(state), ptr(alphas), ptr(betas),
+                                        int(it_begin), int(n_iter), ptr(scratch), ptr(stop), _stream()),
             "meld_lanczos_steps",
         )
 
     # the same iteration as four stream-ordered phases (row-sharded driver; see filter._lanczos_lmax_phases)
     def lanczos_spmv(self, G, x_full, z_local, y_local, state, dots):
-        pt = self.pt_layout(G)
-        if pt is not None:
-            import ctypes as C
-
-            check(self.lib.meld_pt_lanczos_spmv(C.byref(pt["struct"]), ptr(G.rowptr), ptr(G.dw_dev), G.n_rows, ptr(x_full), G.row_begin,
-                                                ptr(z_local), ptr(y_local), ptr(state), ptr(dots), _stream()), "meld_pt_lanczos_spmv")
-            return
-        check(self.lib.meld_lanczos_spmv(ptr(G.rowptr), ptr(G.col), ptr(G.val), ptr(G.dw_dev), G.n_rows, G.nnz, ptr(x_full), G.row_begin,
-                                         ptr(z_local), ptr(y_local), ptr(state), ptr(dots), _stream()), "meld_lanczos_spmv")
+        check(self.lib.meld_lanczos_spmv(self._operator(G), ptr(x_full), G.row_begin, ptr(z_local), ptr(y_local), ptr(state), ptr(dots),
+                                         _stream()), "meld_lanczos_spmv")
 
     def lanczos_alpha(self, state, dots, nrm2, alphas, it):
         check(self.lib.meld_lanczos_alpha(ptr(state), ptr(dots), ptr(nrm2), ptr(alphas), int(it), _stream()), "meld_lanczos_alpha")

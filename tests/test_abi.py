@@ -40,7 +40,38 @@ def test_geometry_queries_and_argument_checks():
     assert lib.meld_knn_tile_refs() == 64 and lib.meld_knn_block_queries() == 128
     # null pointers are rejected before any launch
     assert lib.meld_scale_f64(None, 1.0, None, 10, None) == -1
-    assert lib.meld_cheby_step(None, None, None, None, 0, 0, 2, None, 0, None, None, None, 1.0, 0.0, 0.0, 0.0, None, None) == -1
+    assert lib.meld_cheby_step(None, 2, None, 0, None, None, None, 1.0, 0.0, 0.0, 0.0, None, None) == -1
+
+
+def test_recurrence_entries_check_their_operator_record():
+    """Each of the six entries that take a ``meld_laplacian_t`` returns -1, naming itself, before any launch: for a NULL
+    record, a record without row pointers, and a record that selects the CSR-stream kernel (``layout == NULL``) without
+    columns.  Every other argument is a plausible non-null address (host memory: nothing may touch it)."""
+    from meld_amd import _lib
+
+    lib = _lib.get_lib()
+    buf = (ctypes.c_double * 1024)()
+    a = ctypes.addressof(buf)
+    no_rowptr = _lib.Laplacian(None, a, a, a, 4, 8, None)
+    no_col = _lib.Laplacian(a, None, a, a, 4, 8, None)
+    calls = {
+        "meld_cheby_step": lambda L: lib.meld_cheby_step(L, 1, a, 0, a, a, a, 1.0, 0.0, -1.0, 0.5, None, None),
+        "meld_cheby_step_wide": lambda L: lib.meld_cheby_step_wide(L, 8, a, 0, a, a, 1.0, 0.0, -1.0, None),
+        "meld_cheby_run": lambda L: lib.meld_cheby_run(None, L, 4, 0, 1, a, a, a, a, 4, 1.0, 0.0, None, None),
+        "meld_lanczos_steps": lambda L: lib.meld_lanczos_steps(L, a, a, a, a, a, a, 0, 1, a, None, None),
+        "meld_lanczos_spmv": lambda L: lib.meld_lanczos_spmv(L, a, 0, a, a, a, a, None),
+        # (a non-null communicator that is never dereferenced: the record is checked first)
+        "meld_lanczos_steps_sharded": lambda L: lib.meld_lanczos_steps_sharded(a, L, 4, 0, a, a, a, a, a, a, a, 0, 1, None),
+    }
+    for name, call in calls.items():
+        for what, rec in (("NULL record", None), ("rowptr NULL", ctypes.byref(no_rowptr)), ("col NULL, no layout", ctypes.byref(no_col))):
+            lib.meld_scale_f64(None, 1.0, None, 10, None)  # (leaves another entry's message behind)
+            assert call(rec) == -1, (name, what)
+            assert lib.meld_last_error().decode().startswith(name + ":"), (name, what, lib.meld_last_error())
+    # the boundary has one entry per operation and no development hooks
+    for gone in ("meld_pt_debug_ablate", "meld_pt_debug_stamps", "meld_pt_cheby_step", "meld_pt_cheby_run", "meld_pt_lanczos_steps",
+                 "meld_pt_lanczos_spmv", "meld_cheby_run_sharded"):
+        assert not hasattr(lib, gone), gone
 
 
 def test_product_never_imports_the_oracle():

@@ -544,7 +544,7 @@ def test_column_statistics_in_one_pass_and_the_scale_they_imply(n, d):
 @pytest.mark.parametrize("n", [9000, 80000])
 def test_sharded_recurrences_enqueued_from_c_equal_the_python_loops(n):
     """On an RCCL group the sharded Chebyshev filter and the sharded Lanczos iterations are ONE C call each
-    (meld_cheby_run_sharded / meld_lanczos_steps_sharded on the library's own communicator: kernel + ncclAllGather (+ the one
+    (meld_cheby_run / meld_lanczos_steps_sharded on the library's own communicator: kernel + ncclAllGather (+ the one
     all-reduce) per step, enqueued back to back); MELD_SHARDED_C_LOOPS=0 restores the per-step Python loops over
     torch.distributed.  Same lmax and densities either way -- on the CSR-stream kernel (9000 cells) and on the panel-tiled
     layout (80000 cells) -- and the C path is the one that ran."""

@@ -61,13 +61,8 @@ def test_tiled_recurrence_matches_oracle(cells5k, p):
     assert _rel(out, out_c) < 1e-13
 
 
-@pytest.mark.parametrize("n,density", [(3, 1.0), (70, 0.3), (257, 0.05), (4481, 0.004), (9000, 0.002), (40000, 0.0005)])
-def test_tiled_step_on_awkward_matrices(n, density):
-    """Tiny graphs, a block boundary inside the row range (4481 > RMAX), empty rows, a dense row, rows longer
-    than a wave; random symmetric sparsity instead of a kNN structure.  One step (y, r) and the p = 1 form
-    with its dot products against a scipy evaluation, and against the CSR-stream kernel."""
-    from meld_amd.graph import HipOps
-
+def _awkward_matrix(n, density):
+    """Random symmetric sparsity with (n > 100) an empty row and a long one; the generator it was drawn from."""
     rng = np.random.default_rng(n)
     A = sparse.random(n, n, density=density, random_state=n, format="lil", dtype=np.float64)
     if n > 100:
@@ -83,6 +78,15 @@ def test_tiled_step_on_awkward_matrices(n, density):
     W.sort_indices()
     if W.nnz == 0:
         W = sparse.csr_matrix(np.array([[0, 1.0, 0], [1.0, 0, 2.0], [0, 2.0, 0]]))
+    return W, rng
+
+
+@pytest.mark.parametrize("n,density", [(3, 1.0), (70, 0.3), (257, 0.05), (4481, 0.004), (9000, 0.002), (40000, 0.0005)])
+def test_tiled_step_on_awkward_matrices(n, density):
+    """Tiny graphs, a block boundary inside the row range (4481 > RMAX), empty rows, a dense row, rows longer
+    than a wave; random symmetric sparsity instead of a kNN structure.  One step (y, r) and the p = 1 form
+    with its dot products against a scipy evaluation, and against the CSR-stream kernel."""
+    W, rng = _awkward_matrix(n, density)
     Gt, Gc = _graph_pair(W)
     dw = np.ravel(W.sum(1))
     for p in (1, 2, 3):
@@ -109,6 +113,62 @@ def test_tiled_step_on_awkward_matrices(n, density):
             outs.append(yd.cpu().numpy())
         assert Gt.info["spmm"] == "tiled"
         assert _rel(outs[0], outs[1]) < 1e-13
+
+
+@pytest.mark.parametrize("p", [1, 2, 3])
+@pytest.mark.parametrize("layout", ["tiled", "csr"])
+def test_cheby_run_equals_stepping_one_call_at_a_time(layout, p):
+    """The one loop of ``meld_cheby_run`` against the same orders stepped one ``cheby_step`` at a time, on the n = 4481 matrix
+    above (a block boundary inside the row range, an empty row, a long one): no step (2 coefficients), the odd first step
+    alone (3), one pair (4), odd plus pair (5).  The accumulator and the buffer ``last`` names: the CSR-stream kernel adds
+    c_k T_k at every step in both forms -- bit for bit; the tiled run touches r every other step -- to rounding (1e-13, the
+    bound between the two kernels above); and both against a scipy evaluation of the recurrence (1e-12)."""
+    W, rng = _awkward_matrix(4481, 0.004)
+    n = W.shape[0]
+    G = _graph_pair(W)[0 if layout == "tiled" else 1]
+    dw = np.ravel(W.sum(1))
+    L = sparse.diags(dw) - W
+    a1 = a2 = 1.01 * dw.max()  # lmax / 2 with Gershgorin's lmax <= 2 max(dw): the polynomials stay bounded
+    alpha2, beta2 = 2.0 / a1, -2.0 * a2 / a1
+    c = rng.normal(size=5)
+    T = [rng.normal(size=(n, p))]
+    T.append((L @ T[0] - a2 * T[0]) / a1)
+    for k in range(2, 5):
+        T.append(alpha2 * (L @ T[k - 1]) + beta2 * T[k - 1] - T[k - 2])
+    r_ref = 0.5 * c[0] * T[0] + c[1] * T[1]
+
+    def dev(a):
+        return torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+    for n_coef in (2, 3, 4, 5):
+        if n_coef > 2:
+            r_ref = r_ref + c[n_coef - 1] * T[n_coef - 1]
+        # stepped: the loop of filter.chebyshev_apply
+        t_old, t_cur, r_s = dev(T[0]), dev(T[1]), dev(0.5 * c[0] * T[0] + c[1] * T[1])
+        for k in range(2, n_coef):
+            G.ops.cheby_step(G, p, t_cur, 0, t_old, t_old, r_s, alpha2, beta2, -1.0, c[k])
+            t_old, t_cur = t_cur, t_old
+        # one call
+        bufs, r_r = [dev(T[0]), dev(T[1])], dev(0.5 * c[0] * T[0] + c[1] * T[1])
+        last = G.ops._cheby_run(G, None, 0, p, bufs[0], bufs[1], r_r, c[:n_coef], alpha2, beta2)
+        torch.cuda.synchronize()
+        assert G.info["spmm"] == layout
+        assert last == (n_coef - 2 + 1) % 2  # T_1 sits in the second buffer; every step moves to the other one
+        t_run = bufs[last]
+        print("%s p=%d n_coef=%d: run vs stepped r %.2e T %.2e; run vs scipy r %.2e T %.2e" % (
+            layout, p, n_coef, _rel(r_r.cpu().numpy(), r_s.cpu().numpy()), _rel(t_run.cpu().numpy(), t_cur.cpu().numpy()),
+            _rel(r_r.cpu().numpy(), r_ref), _rel(t_run.cpu().numpy(), T[n_coef - 1])))
+        if layout == "csr":
+            assert torch.equal(r_r, r_s) and torch.equal(t_run, t_cur)
+        else:
+            assert _rel(r_r.cpu().numpy(), r_s.cpu().numpy()) < 1e-13
+            assert _rel(t_run.cpu().numpy(), t_cur.cpu().numpy()) < 1e-13
+        assert _rel(r_r.cpu().numpy(), r_ref) < 1e-12
+        assert _rel(t_run.cpu().numpy(), T[n_coef - 1]) < 1e-12
+        # and through the public method, which is what the filter calls
+        r_p, b_p = dev(0.5 * c[0] * T[0] + c[1] * T[1]), [dev(T[0]), dev(T[1])]
+        assert G.ops.cheby_run(G, p, b_p[0], b_p[1], r_p, c[:n_coef], alpha2, beta2) is True
+        assert torch.equal(r_p, r_r) if layout == "csr" else _rel(r_p.cpu().numpy(), r_r.cpu().numpy()) < 1e-13
 
 
 def test_tiled_layout_holds_every_nonzero_once_and_is_reproducible():

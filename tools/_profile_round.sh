@@ -31,7 +31,7 @@ for v in d.values():
 json.dump(d, open(sys.argv[1], "w"), indent=1, sort_keys=True)
 PY
 { stamp; bash tools/pmc_knn.sh gpurun_out/pmc_knn_$tag 1000000 2>&1 | grep -v "^pass"; } > $out/pmc/knn16_pmc_summary.txt
-{ stamp; bash tools/pmc_spmm.sh gpurun_out/pmc_spmm_$tag 1000000 0 2>&1 | grep -v "^pass\|^saved"; } > $out/pmc/spmm_pmc_summary.txt
+{ stamp; bash tools/pmc_spmm.sh ${out%/*}/pmc_spmm_$tag 1000000 2>&1 | grep -v "^pass\|^saved"; } > $out/pmc/spmm_pmc_summary.txt
 # the search kernel's L2 counters ride in traffic.json too (hit / miss / fabric reads / L1->L2 read latency per launch)
 python - $out/pmc/knn16_pmc_summary.txt $out/pmc/traffic.json $commit <<'PY'
 import json, sys
@@ -51,7 +51,7 @@ if vals:
 json.dump(d, open(sys.argv[2], "w"), indent=1, sort_keys=True)
 PY
 rm -rf gpurun_out/pmc_knn_$tag gpurun_out/pmc_spmm_$tag
-{ stamp; python tools/save_graph.py 1000000 /tmp/g1m.pt > /dev/null; for p in 2 1; do echo "## p = $p"; python tools/spmm_stamps.py /tmp/g1m.pt $p 2>/dev/null; done; python tools/spmm_time.py /tmp/g1m.pt 2>/dev/null | grep "tiled p\|lanczos"; } > $out/recurrence_step_timeline.txt
+{ stamp; python tools/save_graph.py 1000000 /tmp/g1m.pt > /dev/null; python tools/spmm_time.py /tmp/g1m.pt 2>/dev/null | grep "tiled p\|lanczos"; } > $out/recurrence_step_timeline.txt
 { stamp; echo "# the lmax estimate: wall time, serial convergence checks (MELD_LANCZOS_SPECULATE=0) against checks overlapped with the next batch: tools/time_lmax_sizes.py"
   for sp in 0 1; do MELD_LANCZOS_SPECULATE=$sp python tools/time_lmax_sizes.py 1000000 500000 200000 2>&1 | grep "^N="; done; } > $out/lmax.txt
 { stamp; for n in 1000000 500000; do echo "## N = $n"; MELD_COMMIT=$commit MELD_CPU_FULL_JSON=$out/cpu_full_size.json python tools/parity_200k.py $n 2>&1 | grep -v amdgpu.ids; done; } > $out/full_oracle_parity.txt
@@ -99,7 +99,7 @@ PY
   } > $out/knn_ablation.txt
 { stamp; echo "# per-rank compute of the sharded driver on ONE GPU (stand-in collectives, results wrong by construction): tools/shard_emulate.py"
   for g in 2 4 8; do python tools/shard_emulate.py 1000000 $g 1 2>&1 | grep "^rank\|^collectives\|^lmax" | tail -3; done
-  echo "# rank 0 with the recurrences enqueued from C on a REAL one-rank RCCL communicator (RCCL=1: meld_cheby_run_sharded / meld_lanczos_steps_sharded), and the per-step Python loops beside it (RCCL=0)"
+  echo "# rank 0 with the recurrences enqueued from C on a REAL one-rank RCCL communicator (RCCL=1: meld_cheby_run / meld_lanczos_steps_sharded), and the per-step Python loops beside it (RCCL=0)"
   for g in 2 4 8; do for r in 1 0; do echo "## world $g, RCCL=$r"; RCCL=$r python tools/shard_emulate.py 1000000 $g 0 2>&1 | grep "^rank\|^collectives\|^lmax" | tail -3; done; done; } > $out/shard_emulation.txt
 { stamp; echo "# stop rules of the lmax estimate on recorded Lanczos runs (tools/lmax_rule.py): residual rule of the product vs an eigenvalue-error rule"
   python tools/lmax_rule.py 1000000 500000 200000 2>&1 | grep -v amdgpu.ids | grep -v "e+2[0-9][0-9]"; } > $out/lmax_rule.txt

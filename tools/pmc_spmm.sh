@@ -1,15 +1,15 @@
 #!/bin/bash
 export MELD_DEV=1   # (development switches are read only under MELD_DEV=1: meld_amd/_options.py)
-# PMC passes over the recurrence kernel (run on the GPU box): tools/pmc_spmm.sh <outdir> [N] [ablate-mask]
+# PMC passes over the recurrence kernel (run on the GPU box): tools/pmc_spmm.sh <outdir> [N]
 # One rocprofv3 run per counter set (counters + kernel trace only).  Prints per-dispatch averages per kernel.
-out=${1:-gpurun_out/pmc_spmm}; N=${2:-1000000}; AB=${3:-0}
+out=${1:?usage: tools/pmc_spmm.sh <outdir> [N]}; N=${2:-1000000}
 mkdir -p $out; export TMPDIR=/tmp
 [ -f /tmp/g_$N.pt ] || python tools/save_graph.py $N /tmp/g_$N.pt
 i=0
 while read -r set; do
   [ -z "$set" ] && continue
   i=$((i+1))
-  PT_MASK=$AB timeout 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $out/p$i -o pmc -- python tools/spmm_time.py /tmp/g_$N.pt 4 > $out/log_p$i.txt 2>&1
+  timeout 300 rocprofv3 --kernel-trace --pmc $set --output-format csv -d $out/p$i -o pmc -- python tools/spmm_time.py /tmp/g_$N.pt 4 > $out/log_p$i.txt 2>&1
   echo "pass $i ($set): rc=$?"
 done <<SETS
 SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS GRBM_GUI_ACTIVE

@@ -53,7 +53,7 @@ class FakeComm:
 
     def rccl(self):
         """RCCL=1 (rank 0 only: its slice starts at row 0): a REAL one-rank RCCL communicator of the library, so that the
-        recurrences take the C-side loops (meld_cheby_run_sharded / meld_lanczos_steps_sharded) -- kernel + ncclAllGather
+        recurrences take the C-side loops (meld_cheby_run / meld_lanczos_steps_sharded) -- kernel + ncclAllGather
         (+ ncclAllReduce) enqueued per step from one call; the one-rank collectives move nothing, like the stand-ins above,
         but cost their real issue time."""
         if os.environ.get("RCCL") != "1" or self.rank != 0:

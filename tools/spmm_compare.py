@@ -30,9 +30,6 @@ def timed(fn, reps):
 
 
 res = {}
-if os.environ.get("PT_FORCE_ABLATE", "0") != "0":  # profile an ablated variant (tools/pmc_spmm.sh)
-    from meld_amd._lib import get_lib
-    get_lib().meld_pt_debug_ablate(int(os.environ["PT_FORCE_ABLATE"]))
 for mode in ("csr", "tiled"):
     G.pt = None
     G.ops = HipOps(spmm=mode)
@@ -54,16 +51,6 @@ for mode in ("csr", "tiled"):
         ent = np.diff(rp[br])
         print("  layout: nb=%d build %.2f ms; tiles/block mean %.1f max %d; distinct cols/block mean %.0f; rows/block %d..%d; entries/block %d..%d"
               % (G.pt["nb"], 1e3 * t_build, nt.mean(), nt.max(), nd.mean(), np.diff(br).min(), np.diff(br).max(), ent.min(), ent.max()), flush=True)
-    if mode == "tiled" and os.environ.get("PT_BUILD_STAGES", "0") != "0":
-        from meld_amd._lib import get_lib
-        for stage in (1, 2, 3, 0):
-            get_lib().meld_pt_debug_ablate(stage << 8)
-            G.pt = None
-            us = timed(lambda: (setattr(G, "pt", None), G.ops.pt_layout(G)), 3)
-            print("  layout build stopped after stage %d: %.2f ms" % (stage, us / 1e3), flush=True)
-        get_lib().meld_pt_debug_ablate(0)
-        G.pt = None
-        G.ops.pt_layout(G)
     for pp in (p, 1):
         gen = torch.Generator(device="cuda").manual_seed(pp)
         x = torch.rand(n, pp, dtype=torch.float64, device="cuda", generator=gen)
@@ -74,17 +61,6 @@ for mode in ("csr", "tiled"):
         byts = cheby_bytes_per_step(G.nnz, n, pp)
         print("  %-5s p=%d: %.1f us/step  %.0f GB/s algorithmic = %.3f of 8 TB/s" % (mode, pp, us, byts / us / 1e3, byts / us / 1e3 / 8000), flush=True)
         res[(mode, pp)] = y.cpu().numpy().copy()
-if os.environ.get("PT_ABLATE", "1") != "0":
-    from meld_amd._lib import get_lib
-    lib = get_lib()
-    for mask, what in ((4, "no panel loads"), (8, "panel gathers from a 16 KB window"), (16, "consumers ignore panel readiness")):
-        lib.meld_pt_debug_ablate(mask)
-        for pp in (p, 1):
-            x = torch.rand(n, pp, dtype=torch.float64, device="cuda")
-            y = torch.empty_like(x)
-            us = timed(lambda: G.ops.cheby_step(G, pp, x, 0, x, y, None, 0.7, -0.2, -1.0, 0.1), 20)
-            print("  ablation %d (%s) p=%d: %.1f us/step" % (mask, what, pp, us), flush=True)
-    lib.meld_pt_debug_ablate(0)
 for pp in (p, 1):
     a, b = res[("csr", pp)], res[("tiled", pp)]
     print("  max |tiled - csr| / max|csr| (p=%d): %.2e" % (pp, np.abs(a - b).max() / np.abs(b).max()))

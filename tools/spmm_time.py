@@ -39,9 +39,7 @@ def timed(fn, reps):
     return min(ts), float(np.median(ts))
 
 
-from meld_amd._lib import get_lib
 res = {}
-MASK = int(os.environ.get("PT_MASK", "0"))  # timing-only ablation mask of meld_pt_debug_ablate (results wrong)
 for mode in ("csr", "tiled"):
     G.pt = None
     G.ops = HipOps(spmm=mode)
@@ -55,10 +53,6 @@ for mode in ("csr", "tiled"):
         G.ops.cheby_step(G, pp, x, 0, z, y, r, 0.7, -0.2, -1.0, 0.1)
         res[(mode, pp)] = y.cpu().numpy().copy()
         if mode == "tiled":
-            if MASK:
-                from meld_amd._lib import get_lib
-                get_lib().meld_pt_debug_ablate(MASK)
-                tag = tag.split(" mask")[0] + " mask%d" % MASK
             # ping-pong like the filter does (x and y swap every step)
             bufs = [x, y]
             state = {"i": 0}
