@@ -461,6 +461,25 @@ int meld_csr_anisotropy_degrees(const int64_t* rowptr, const int32_t* col, doubl
                                 const double* ksum_all, int64_t ksum_row_offset, double anisotropy, double* dw,
                                 meld_stream_t stream);
 
+/* ---- out-of-sample extension (csrc/extend.hip; replaces [UPSTREAM graphtools 1.5.x kNNGraph.build_kernel_to_data(Y),
+ *      BaseGraph.extend_to_data(Y), BaseGraph.interpolate(transform, transitions)], reached through `meld_op.graph`) ---- */
+
+/* The query-major half of the COO stream of a search between two point sets (meld_coo_emit: keys (row << 32) | ref, values
+ * K / 2, rows in any order) -> the rectangular CSR of rows [row_begin, row_begin + n_rows): rowptr[n_rows + 1] (int64), col[n]
+ * (int32, sorted inside a row), val[n] = K, rowsum[n_rows] = the rows' sums (meld_csr_row_sums' bits, diag 0).  Entries of other
+ * rows, or with a column >= n_cols, are ignored (rowptr[n_rows] <= n entries are written).  Equal columns inside a row are NOT
+ * merged (the stream has none).  The same bits every run.  temp: meld_extend_rows_temp_bytes(n, n_rows) bytes, 8-byte aligned. */
+size_t meld_extend_rows_temp_bytes(int64_t n, int64_t n_rows);
+int meld_extend_rows(const uint64_t* keys, const double* half_vals, int64_t n, int64_t row_begin, int64_t n_rows, int64_t n_cols,
+                     int64_t* rowptr, int32_t* col, double* val, double* rowsum, void* temp, size_t temp_bytes,
+                     meld_stream_t stream);
+/* out[n_rows, p] = diag(1 / rowsum) K F: the transitions of the new cells applied to a signal on the fitted cells, fp64, without
+ * writing the transitions.  F: [n_f_rows, p] row-major, p >= 1.  colmap (optional, int64[n_f_rows]): row of F that holds column
+ * j of K (F in the graph's device order: the inverse of its permutation); NULL: row j.  A column outside [0, n_f_rows) adds
+ * nothing; a row whose sum is not positive gives zeros.  One wave per row, no atomics: the same bits every run. */
+int meld_extend_apply(const int64_t* rowptr, const int32_t* col, const double* val, const double* rowsum, int64_t n_rows,
+                      const double* F, int64_t n_f_rows, int p, const int64_t* colmap, double* out, meld_stream_t stream);
+
 /* ---- Laplacian operator: lmax and the Chebyshev recurrence (replaces [UPSTREAM pygsp
  *      Graph.estimate_lmax] at meld/filter.py:39 and [UPSTREAM pygsp
  *      filters.approximations.cheby_op] at meld/filter.py:59) ------------------------------- */

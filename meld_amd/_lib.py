@@ -110,6 +110,9 @@ SIGNATURES = {
     "meld_csr_row_sums": (_i32, [_ptr, _ptr, _i64, _f64, _ptr, _ptr]),
     "meld_csr_anisotropy": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _i64, _f64, _ptr]),
     "meld_csr_anisotropy_degrees": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _i64, _f64, _ptr, _ptr]),
+    "meld_extend_rows_temp_bytes": (_sz, [_i64, _i64]),
+    "meld_extend_rows": (_i32, [_ptr, _ptr, _i64, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _sz, _ptr]),
+    "meld_extend_apply": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _i32, _ptr, _ptr, _ptr]),
     "meld_spmm_dot_slots": (_i32, []),
     # (the first _ptr of the recurrence entries: a Laplacian record, by reference)
     "meld_cheby_step": (_i32, [_ptr, _i32, _ptr, _i64, _ptr, _ptr, _ptr, _f64, _f64, _f64, _f64, _ptr, _ptr]),

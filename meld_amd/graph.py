@@ -408,6 +408,60 @@ class DeviceGraph:
             return torch.ones(self.N, dtype=torch.float64, device=self.val.device)
         return 1.0 / (self.ksum * self.ksum) ** self.anisotropy
 
+    # -- out-of-sample extension (meld_amd/extend.py, csrc/extend.hip): graphtools' names and semantics for cells that were not
+    # in ``fit``.  Graphs without cells or without a comparable kernel raise NotImplementedError, naming the case. -------------
+    @property
+    def n_features_in(self):
+        """Columns of the data ``fit`` received (None where the graph was not built from cells by ``MELD.fit``)."""
+        st = getattr(self, "_extend_state", None)
+        return None if st is None else st.n_features_in
+
+    def kernel_to_data_device(self, Y, knn=None, bandwidth=None, bandwidth_scale=None):
+        """The kernel from the new cells ``Y`` to the fitted cells as device tensors ``(rowptr, col, val, rowsum)``: CSR
+        ``[M, N]``, columns in the caller's cell order and sorted, with its row sums; nothing goes through the host."""
+        from . import extend
+
+        return extend.kernel_to_data_device(self, Y, knn=knn, bandwidth=bandwidth, bandwidth_scale=bandwidth_scale)
+
+    def build_kernel_to_data(self, Y, knn=None, bandwidth=None, bandwidth_scale=None):
+        """[UPSTREAM graphtools 1.5.x ``kNNGraph.build_kernel_to_data``]: scipy CSR ``[M, N]`` (a host export, like ``K``):
+        ``exp(-(dist / bw)^decay)`` for every fitted cell with a value >= thresh, ``bw`` the distance to the knn-th nearest
+        FITTED cell (or the graph's fixed numeric bandwidth) times ``bandwidth_scale``, floored at eps; ``decay=None``: the
+        connectivity of the knn nearest fitted cells.  ``Y``: ``n_features_in`` columns (projected with the stored PCA / SVD
+        model and the metric's front end) or the reduced number of columns."""
+        from . import extend
+
+        return extend.to_scipy(self.kernel_to_data_device(Y, knn=knn, bandwidth=bandwidth, bandwidth_scale=bandwidth_scale), self.N)
+
+    def extend_to_data(self, Y):
+        """[UPSTREAM graphtools ``BaseGraph.extend_to_data``]: the transitions ``[M, N]`` from new cells to fitted cells, the
+        kernel of ``build_kernel_to_data`` l1-normalised by row (scipy CSR)."""
+        from . import extend
+
+        return extend.to_scipy(self.kernel_to_data_device(Y), self.N, normalise=True)
+
+    def interpolate(self, transform, transitions=None, Y=None):
+        """[UPSTREAM graphtools ``BaseGraph.interpolate``]: ``transitions @ transform`` for a ``transform`` with one row per
+        fitted cell (caller's order).  With ``Y`` the product runs on the device and the transitions are never written;
+        a scipy ``transitions`` is multiplied on the host."""
+        from . import extend
+
+        return extend.interpolate(self, transform, transitions=transitions, Y=Y)
+
+    def interpolate_device(self, F, Y, device_order=False):
+        """``interpolate(F, Y=Y)`` for a device tensor ``F [N, p]``, returning a device tensor ``[M, p]``.  ``device_order``:
+        the rows of ``F`` are in the graph's device order (``perm``), the kernel's columns are translated on the fly."""
+        from . import extend
+
+        colmap = None
+        if device_order and self.perm is not None:
+            colmap = torch.empty_like(self.perm)
+            colmap[self.perm] = torch.arange(self.perm.shape[0], device=self.perm.device, dtype=self.perm.dtype)
+        extend.state_of(self)
+        if F.dim() != 2 or int(F.shape[0]) != self.N:
+            raise ValueError("transform must have one row per fitted cell ({}), got shape {}".format(self.N, tuple(F.shape)))
+        return extend.apply_transitions(self.kernel_to_data_device(Y), F.to(torch.float64), colmap=colmap)
+
 
 _BLAS_CTL = None
 

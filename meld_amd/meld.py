@@ -148,6 +148,7 @@ class MELD(GraphEstimator):
         from . import sparse as _sparse
 
         svd_scores = None
+        project = n_features_in = None  # (kept on the graph for new cells: meld_amd/extend.py)
         if _sparse.is_sparse_input(data):
             # sparse input (meld_amd/sparse.py): graphtools reduces it with an UNCENTRED truncated SVD where it reduces at all
             # (Data._reduce_data); without a reduction, and for precomputed matrices, it is densified on the device and takes
@@ -155,7 +156,10 @@ class MELD(GraphEstimator):
             A = _sparse.DeviceCSR.from_input(data)
             if (self.n_pca is not None and self.n_pca < min(A.shape)) and not str(self.distance).lower().startswith("precomputed"):
                 self._log("Calculating truncated SVD ({} components)...".format(self.n_pca))
-                svd_scores = _sparse.truncated_svd_project(A, self.n_pca, seed=42 if self.random_state is None else int(self.random_state))
+                svd_scores, svd_v = _sparse.truncated_svd_project(A, self.n_pca, seed=42 if self.random_state is None else int(self.random_state),
+                                                                  return_model=True)
+                project = lambda Q, V=svd_v: Q @ V  # noqa: E731  (graphtools' TruncatedSVD: uncentred)
+                n_features_in = int(A.shape[1])
                 data = svd_scores
             else:
                 data = A.to_dense()
@@ -200,7 +204,9 @@ class MELD(GraphEstimator):
             from .pca import pca_project
 
             self._log("Calculating PCA ({} components)...".format(self.n_pca))
-            X = pca_project(X, self.n_pca, seed=42 if self.random_state is None else int(self.random_state))
+            n_features_in = int(X.shape[1])
+            X, pca_mean, pca_v = pca_project(X, self.n_pca, seed=42 if self.random_state is None else int(self.random_state), return_model=True)
+            project = lambda Q, mean=pca_mean, V=pca_v: (Q - mean) @ V  # noqa: E731
             self.data_nu = X
         from .graph import metric_front_end
 
@@ -276,6 +282,15 @@ class MELD(GraphEstimator):
             kernel_symm=opts.get("kernel_symm", "+"), theta=opts.get("theta"), ops=ops0,
         )
         G.bandwidth_to_metric = bw_to_metric
+        # what new cells need (DeviceGraph.build_kernel_to_data / extend_to_data / interpolate): the matrix the search saw, in the
+        # caller's order (a reference: the graph pins it), the model that maps a raw cell to it, the kernel's parameters
+        from .extend import attach_extension_state
+
+        distance = str(self.distance).lower()
+        row_fn = None if distance in ("euclidean", "l2", "sqeuclidean") else (lambda Q, m=distance: metric_front_end(Q, m, None)[0])
+        attach_extension_state(G, X, X.shape[1] if n_features_in is None else n_features_in, project, row_fn, knn=int(self.knn),
+                               decay=float("inf") if decay_m is None else decay_m, thresh=self.thresh, bandwidth=bw_opts.get("bandwidth"),
+                               bandwidth_scale=bw_opts.get("bandwidth_scale"), knn_max=bw_opts.get("knn_max"), ksel=opts.get("ksel"))
         # n_landmark (reference meld/meld.py:105,118 forwards it to graphtools): a graphtools LandmarkGraph has the
         # same kernel, weights and Laplacian as the plain kNN graph -- the landmark operator is a lazily built extra
         # (`landmark_op`, `transitions`, `interpolate`) that MELD's filter never touches -- so the densities do not
@@ -508,6 +523,22 @@ class MELD(GraphEstimator):
         self.beta = saved
         self.sample_densities = first
         return out
+
+    def transform_new(self, Y):
+        """The fitted sample densities interpolated to cells that were not in ``fit``: ``graph.interpolate(sample_densities,
+        Y=Y)`` -- the kernel from the new cells to the fitted ones ([UPSTREAM graphtools ``kNNGraph.build_kernel_to_data``]),
+        l1-normalised by row, applied to the densities on the device.  ``Y``: array, tensor or DataFrame with the columns of
+        the data ``fit`` saw (or the reduced ones).  Returns a DataFrame ``[M, p]`` with the columns of ``sample_densities``
+        and ``Y``'s index where it has one; ``meld.utils.normalize_densities`` applies to it as it is.  Call after
+        ``transform`` / ``fit_transform``."""
+        if self.sample_densities is None or self.graph is None:
+            raise ValueError("sample_densities must be set prior to running transform_new(): call transform() or fit_transform() first.")
+        G = self.graph
+        if not hasattr(G, "interpolate"):
+            raise NotImplementedError("the graph of this estimator cannot be extended to new cells")
+        values = G.interpolate(np.ascontiguousarray(self.sample_densities.values, dtype=np.float64), Y=Y)
+        index = Y.index if isinstance(Y, (pd.DataFrame, pd.Series)) else None
+        return pd.DataFrame(values, index=index, columns=self.sample_densities.columns)
 
     def fit_transform(self, X, sample_labels, **kwargs):
         """Builds the graph on ``X`` and estimates the density of each sample in
