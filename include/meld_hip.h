@@ -367,6 +367,40 @@ int meld_metric_radius(const double* X, int64_t N, int d, int metric, const int3
                        double decay, double thresh, int mode, int32_t* fb_cnt, const int64_t* fb_off, int32_t* fb_cursor,
                        int32_t* fb_col, double* fb_val, meld_stream_t stream);
 
+/* ---- the same, between two point sets: queries Q [M][d] that are NOT among the references X [N][d] (new cells against a fitted
+ *      graph: meld_amd/extend.py).  The arithmetic and the (distance, column) order are those above; a
+ *      query has no self entry and nothing is dropped as a diagonal.  X, box_lo, box_hi as meld_metric_tile_boxes takes and
+ *      writes them. ------------------------------------------------------------------------------------------------------------
+ * Slices of the reference tiles the search of M queries is split into (grid.y; every slice keeps heaps of its own, a merge
+ * keeps the ksel smallest: the lists are the same bits for any count).  n_slices = 0: chosen from M and the device's CU count;
+ * otherwise n_slices clipped to [1, min(16, tiles)].  Size the scratch of meld_metric_cross_topk with the value returned. */
+int meld_metric_cross_slices(int64_t M, int64_t N, int n_slices);
+/* seed_key[M] (every bit set on entry) <- (point-to-box bound as fp32 bits << 32) | tile of the reference tile nearest to each
+ * query: the low 32 bits are the tile the search starts from.  n_tiles * d operations per query.  Qt [d][M]: the queries
+ * TRANSPOSED (lane = query: the reads of one coordinate coalesce). */
+int meld_metric_cross_seed(const double* Qt, int64_t M, const double* box_lo, const double* box_hi, int64_t N, int d, int metric,
+                           unsigned long long* seed_key, meld_stream_t stream);
+/* Every query's ksel nearest references by (distance, column), exactly, ascending: cand_idx / cand_d [M][ksel], cand_cnt[M] =
+ * min(ksel, N).  Qt [d][M]: the queries transposed.  One wave per 64 consecutive queries: sort the queries by seed tile for the
+ * pruning to bite (any order and any seed in [0, tiles) gives the same lists).  A tile is skipped when the bound of its box
+ * against the wave's box exceeds every lane's heap top, or when every lane's own point-to-box bound exceeds that lane's.
+ * heap_d / heap_i: n_slices * ksel * ceil(M / 64) * 64 entries each; part_idx /
+ * part_d [n_slices][M][ksel] and part_cnt [n_slices][M]: the slices' lists (may be NULL when n_slices == 1).  prune = 0 visits
+ * every tile.  tiles_done[0] (zeroed by the caller) += (query tile, reference tile) pairs computed. */
+int meld_metric_cross_topk(const double* Qt, int64_t M, const double* X, int64_t N, int d, int metric, int ksel, const double* box_lo,
+                           const double* box_hi, const int32_t* seed, int prune, int n_slices, double* heap_d, int32_t* heap_i,
+                           int32_t* part_idx, double* part_d, int32_t* part_cnt, int32_t* cand_idx, double* cand_d, int32_t* cand_cnt,
+                           unsigned long long* tiles_done, meld_stream_t stream);
+/* meld_metric_refine for queries: bw[M] = max(bw_scale * (knn+1)-th distance, eps) (pass knn = knn_c - 1: the knn_c-th nearest
+ * reference), no entry is the row itself; decay = +inf keeps the first knn + 1 entries of a list, whatever their distances. */
+int meld_metric_cross_refine(const int32_t* cand_idx, const double* cand_d, const int32_t* cand_cnt, int64_t M, int ksel, int knn,
+                             double decay, double thresh, double bw_scale, double* bw, double* cand_val, int32_t* keep_cnt,
+                             int32_t* flag_rows, int32_t* n_flag, meld_stream_t stream);
+/* meld_metric_radius for queries: the flagged rows are rows of Q, bw [M] is final (scaled, floored), every reference counts. */
+int meld_metric_cross_radius(const double* Q, int64_t M, const double* X, int64_t N, int d, int metric, const int32_t* flag_rows,
+                             int32_t n_flag, const double* bw, double decay, double thresh, int mode, int32_t* fb_cnt,
+                             const int64_t* fb_off, int32_t* fb_cursor, int32_t* fb_col, double* fb_val, meld_stream_t stream);
+
 /* ---- symmetrise / anisotropy / Laplacian pieces (replaces [UPSTREAM graphtools
  *      BaseGraph.symmetrize_kernel, apply_anisotropy, PyGSPGraph._build_weight_from_kernel;
  *      pygsp Graph.compute_laplacian]) ------------------------------------------------------- */

@@ -83,6 +83,12 @@ SIGNATURES = {
     "meld_metric_topk": (_i32, [_ptr, _i64, _i32, _i32, _i32, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "meld_metric_refine": (_i32, [_ptr, _ptr, _ptr, _i64, _i32, _i32, _f64, _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "meld_metric_radius": (_i32, [_ptr, _i64, _i32, _i32, _ptr, _i32, _ptr, _f64, _f64, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "meld_metric_cross_slices": (_i32, [_i64, _i64, _i32]),
+    "meld_metric_cross_seed": (_i32, [_ptr, _i64, _ptr, _ptr, _i64, _i32, _i32, _ptr, _ptr]),
+    "meld_metric_cross_topk": (_i32, [_ptr, _i64, _ptr, _i64, _i32, _i32, _i32, _ptr, _ptr, _ptr, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr,
+                                      _ptr, _ptr, _ptr, _ptr]),
+    "meld_metric_cross_refine": (_i32, [_ptr, _ptr, _ptr, _i64, _i32, _i32, _f64, _f64, _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "meld_metric_cross_radius": (_i32, [_ptr, _i64, _ptr, _i64, _i32, _i32, _ptr, _i32, _ptr, _f64, _f64, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "meld_scan_temp_bytes": (_sz, [_i64]),
     "meld_exclusive_scan_i32_i64": (_i32, [_ptr, _ptr, _i64, _ptr, _sz, _ptr]),
     "meld_coo_emit": (

@@ -10,6 +10,7 @@ The graph object the reference hands out (``meld_op.graph``, a graphtools ``kNNG
   cells stacked behind the fitted ones chunk by chunk; the bandwidth of a new cell is the distance to its knn-th nearest FITTED
   cell (it is not among them), as ``oracle.kernel_to_data`` restates upstream.  Data wider than the search kernels keep the
   library route (``mnn.cross_kernel``), a fixed numeric ``bandwidth`` takes a library route of its own (``_fixed_bandwidth_kernel``);
+  the L1 / L-inf graphs take the exact search of ``csrc/metric_knn.hip`` (``metric_knn.cross_kernel_rows``);
 * ``csrc/extend.hip`` turns the query-major half of the COO stream into the rectangular CSR ``[M, N]`` with its row sums
   (``meld_extend_rows``) and applies the row-normalised rows to a signal on the fitted cells without writing the transitions
   (``meld_extend_apply``).
@@ -47,10 +48,11 @@ class ExtensionState(SimpleNamespace):
 
 
 def attach_extension_state(G, X, n_features_in, project, row_fn, knn, decay, thresh, bandwidth=None, bandwidth_scale=None, knn_max=None,
-                           ksel=None):
+                           ksel=None, metric=None, model=None):
     G._extend_state = ExtensionState(X=X, n_features_in=int(n_features_in), project=project, row_fn=row_fn, knn=int(knn),
                                      decay=float(decay), thresh=float(thresh), bandwidth=bandwidth,
-                                     bandwidth_scale=1.0 if bandwidth_scale is None else float(bandwidth_scale), knn_max=knn_max, ksel=ksel)
+                                     bandwidth_scale=1.0 if bandwidth_scale is None else float(bandwidth_scale), knn_max=knn_max, ksel=ksel,
+                                     metric=metric, model=model)
     return G
 
 
@@ -63,9 +65,10 @@ def refusal(G):
         return "a graph adopted from {} keeps neither its cells nor its kernel's parameters: it cannot be extended to new cells".format(info["adopted_from"])
     if info.get("graph") == "mnn":
         return "an MNN graph (sample_idx) cannot be extended to new cells: a new cell belongs to no sample"
-    if info.get("route") == "metric_knn" or info.get("metric") in ("manhattan", "cityblock", "l1", "chebyshev"):
+    l1 = getattr(getattr(G, "_extend_state", None), "metric", None) is not None  # (an L1 / L-inf graph that kept its cells)
+    if not l1 and (info.get("route") == "metric_knn" or info.get("metric") in ("manhattan", "cityblock", "l1", "chebyshev")):
         return "the L1 / L-inf graphs (distance={!r}) cannot be extended to new cells: the search between two point sets is euclidean".format(info.get("metric"))
-    if info.get("dense"):
+    if not l1 and info.get("dense"):
         return ("a dense graph (thresh=0, a precomputed matrix, or a kernel evaluated densely) cannot be extended to new cells: "
                 "only the sparse euclidean kNN graph keeps a comparable kernel")
     if getattr(G, "_extend_state", None) is None:
@@ -111,19 +114,48 @@ def _to_device(Y, dev):
     return torch.from_numpy(np.ascontiguousarray(Y, dtype=np.float64)).to(dev)
 
 
+def _project_sparse(st, Y, dev):
+    """Sparse new cells -> the d columns, on the device and without a dense copy of ``Y`` where the graph reduced its data:
+    ``Y V`` (sparse fit: the truncated SVD, uncentred) or ``Y V - mean V`` (dense fit: PCA) through ``DeviceCSR.matmul``; without
+    a reduction the rows are densified (they are as wide as the search's own operands)."""
+    from .sparse import DeviceCSR
+
+    A = DeviceCSR.from_input(Y, device=dev)
+    d = int(st.X.shape[1])
+    kind = check_extension_shape(A.shape, st.n_features_in, d)
+    if kind == "reduced":  # (scores are dense by nature: a sparse matrix of that width is a mistake)
+        raise ValueError("Y must be of shape either (n, {}) or (n, {})".format(st.n_features_in, d) + ": sparse input has to carry the {} "
+                         "columns of the data".format(st.n_features_in))
+    model = getattr(st, "model", None)
+    if model is None:
+        if st.project is not None:
+            raise NotImplementedError("this graph keeps its projection as a function only: sparse new cells need the model")
+        return A.to_dense()
+    Q = A.matmul(model["V"])
+    if model["kind"] == "pca":
+        Q -= model["mean"].reshape(1, -1).to(torch.float64) @ model["V"]
+    return Q
+
+
 def prepare_queries(st, Y):
-    """New cells -> the space the search ran in: shape check, the stored projection, the metric's row front end."""
+    """New cells -> the space the search ran in: shape check, the stored projection, the metric's row front end.  ``Y``: an
+    array, a tensor, a DataFrame, or whatever ``sparse.is_sparse_input`` accepts."""
+    from .sparse import is_sparse_input
+
     dev = st.X.device
     d = int(st.X.shape[1])
-    shape = tuple(getattr(Y, "shape", np.shape(Y)))
-    kind = check_extension_shape(shape, st.n_features_in, d)
-    Q = _to_device(Y, dev)
-    if Q.shape[0] == 0:
-        raise ValueError("Y holds no cells")
-    if not bool(torch.isfinite(Q.sum(dim=0)).all()) and not bool(torch.isfinite(Q).all()):
-        raise ValueError("Input data contains NaN or infinity")
-    if kind == "raw" and st.project is not None:
-        Q = st.project(Q)
+    if is_sparse_input(Y):
+        Q = _project_sparse(st, Y, dev)  # (checks shape, structure and finiteness on the way)
+    else:
+        shape = tuple(getattr(Y, "shape", np.shape(Y)))
+        kind = check_extension_shape(shape, st.n_features_in, d)
+        Q = _to_device(Y, dev)
+        if Q.shape[0] == 0:
+            raise ValueError("Y holds no cells")
+        if not bool(torch.isfinite(Q.sum(dim=0)).all()) and not bool(torch.isfinite(Q).all()):
+            raise ValueError("Input data contains NaN or infinity")
+        if kind == "raw" and st.project is not None:
+            Q = st.project(Q)
     if st.row_fn is not None:
         Q = st.row_fn(Q)
     return Q.contiguous()
@@ -234,10 +266,22 @@ def _stack_scaled(ops, Xr, Qc):
     return Xcat, (sums, cmin, cmax)
 
 
-def kernel_to_data_device(G, Y, knn=None, bandwidth=None, bandwidth_scale=None):
+def _concat_rows(parts):
+    """Row blocks (rowptr, col, val, rowsum) of consecutive new cells -> one CSR."""
+    if len(parts) == 1:
+        return parts[0]
+    offs, rowptrs = 0, []
+    for i, p in enumerate(parts):
+        rowptrs.append((p[0] if i == len(parts) - 1 else p[0][:-1]) + offs)
+        offs += int(p[1].shape[0])
+    return torch.cat(rowptrs), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]), torch.cat([p[3] for p in parts])
+
+
+def kernel_to_data_device(G, Y, knn=None, bandwidth=None, bandwidth_scale=None, n_slices=0):
     """The kernel from the new cells ``Y`` to the fitted cells as device tensors ``(rowptr int64 [M + 1], col int32, val fp64,
     rowsum fp64 [M])``: rectangular CSR ``[M, N]``, columns in the caller's cell order, sorted inside a row.  Nothing goes
-    through the host."""
+    through the host.  ``n_slices`` (L1 / L-inf graphs): slices of the fitted cells the search of few new cells is split into,
+    0 = chosen from their number and the device; the result does not depend on it."""
     from .graph import HipOps, default_ksel
     from .mnn import cross_kernel
 
@@ -260,6 +304,10 @@ def kernel_to_data_device(G, Y, knn=None, bandwidth=None, bandwidth_scale=None):
     Xr = st.X
     N, d, M = int(Xr.shape[0]), int(Xr.shape[1]), int(Q.shape[0])
     knn_c = int(min(knn, N))  # graphtools clips knn to the number of fitted cells
+    if getattr(st, "metric", None) is not None:
+        from .metric_knn import cross_kernel_rows
+
+        return _concat_rows(cross_kernel_rows(G, st, Q, knn_c, decay, thresh, bandwidth=bw, scale=scale, n_slices=n_slices))
     ops = G.ops if getattr(G, "ops", None) is not None else HipOps(Xr.device)
     ks = default_ksel(knn_c) if st.ksel is None else max(int(st.ksel), default_ksel(knn_c))
     hot = bw is None and ops.search == "f16x3" and ops.lib.meld_knn16_kblocks(d) >= 0 and knn_c >= 2 and N >= 3 and ks >= knn_c + 1
@@ -282,13 +330,7 @@ def kernel_to_data_device(G, Y, knn=None, bandwidth=None, bandwidth_scale=None):
         else:
             r, c, v = cross_kernel(Qc, Xr, knn_c, decay, thresh)
         parts.append(extend_rows(((r << 32) | c).contiguous(), (0.5 * v).contiguous(), 0, m, N))
-    if len(parts) == 1:
-        return parts[0]
-    offs, rowptrs = 0, []
-    for i, p in enumerate(parts):
-        rowptrs.append((p[0] if i == len(parts) - 1 else p[0][:-1]) + offs)
-        offs += int(p[1].shape[0])
-    return torch.cat(rowptrs), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]), torch.cat([p[3] for p in parts])
+    return _concat_rows(parts)
 
 
 def to_scipy(csr, N, normalise=False):

@@ -416,12 +416,13 @@ class DeviceGraph:
         st = getattr(self, "_extend_state", None)
         return None if st is None else st.n_features_in
 
-    def kernel_to_data_device(self, Y, knn=None, bandwidth=None, bandwidth_scale=None):
+    def kernel_to_data_device(self, Y, knn=None, bandwidth=None, bandwidth_scale=None, n_slices=0):
         """The kernel from the new cells ``Y`` to the fitted cells as device tensors ``(rowptr, col, val, rowsum)``: CSR
-        ``[M, N]``, columns in the caller's cell order and sorted, with its row sums; nothing goes through the host."""
+        ``[M, N]``, columns in the caller's cell order and sorted, with its row sums; nothing goes through the host.
+        ``n_slices``: see ``extend.kernel_to_data_device`` (L1 / L-inf graphs; the result does not depend on it)."""
         from . import extend
 
-        return extend.kernel_to_data_device(self, Y, knn=knn, bandwidth=bandwidth, bandwidth_scale=bandwidth_scale)
+        return extend.kernel_to_data_device(self, Y, knn=knn, bandwidth=bandwidth, bandwidth_scale=bandwidth_scale, n_slices=n_slices)
 
     def build_kernel_to_data(self, Y, knn=None, bandwidth=None, bandwidth_scale=None):
         """[UPSTREAM graphtools 1.5.x ``kNNGraph.build_kernel_to_data``]: scipy CSR ``[M, N]`` (a host export, like ``K``):

@@ -148,7 +148,7 @@ class MELD(GraphEstimator):
         from . import sparse as _sparse
 
         svd_scores = None
-        project = n_features_in = None  # (kept on the graph for new cells: meld_amd/extend.py)
+        project = n_features_in = model = None  # (kept on the graph for new cells: meld_amd/extend.py)
         if _sparse.is_sparse_input(data):
             # sparse input (meld_amd/sparse.py): graphtools reduces it with an UNCENTRED truncated SVD where it reduces at all
             # (Data._reduce_data); without a reduction, and for precomputed matrices, it is densified on the device and takes
@@ -159,6 +159,7 @@ class MELD(GraphEstimator):
                 svd_scores, svd_v = _sparse.truncated_svd_project(A, self.n_pca, seed=42 if self.random_state is None else int(self.random_state),
                                                                   return_model=True)
                 project = lambda Q, V=svd_v: Q @ V  # noqa: E731  (graphtools' TruncatedSVD: uncentred)
+                model = dict(kind="svd", V=svd_v)
                 n_features_in = int(A.shape[1])
                 data = svd_scores
             else:
@@ -207,6 +208,7 @@ class MELD(GraphEstimator):
             n_features_in = int(X.shape[1])
             X, pca_mean, pca_v = pca_project(X, self.n_pca, seed=42 if self.random_state is None else int(self.random_state), return_model=True)
             project = lambda Q, mean=pca_mean, V=pca_v: (Q - mean) @ V  # noqa: E731
+            model = dict(kind="pca", mean=pca_mean, V=pca_v)
             self.data_nu = X
         from .graph import metric_front_end
 
@@ -221,11 +223,23 @@ class MELD(GraphEstimator):
                 route = metric_route(int(X.shape[0]), int(X.shape[1]), self.knn, self.decay, self.thresh, opts)
             except NotImplementedError:
                 raise NotImplementedError("distance={!r} is implemented for the plain alpha-decay / unweighted kNN graph only".format(self.distance)) from None
+            from .extend import attach_extension_state
+            from .metric_knn import METRICS
+
             if route == "metric_knn":
-                return build_metric_knn_graph(X, self.knn, self.decay, self.thresh, self.anisotropy, str(self.distance).lower(),
-                                              kernel_symm=opts.get("kernel_symm", "+"), theta=opts.get("theta"), ksel=opts.get("ksel"),
-                                              profile=bool(opts.get("profile", False)), ops=ops0)
-            return build_dense_knn_graph(X, self.knn, self.decay, self.thresh, anisotropy=self.anisotropy, symm=symm, metric=str(self.distance).lower())
+                G = build_metric_knn_graph(X, self.knn, self.decay, self.thresh, self.anisotropy, str(self.distance).lower(),
+                                           kernel_symm=opts.get("kernel_symm", "+"), theta=opts.get("theta"), ksel=opts.get("ksel"),
+                                           profile=bool(opts.get("profile", False)), ops=ops0)
+            else:
+                G = build_dense_knn_graph(X, self.knn, self.decay, self.thresh, anisotropy=self.anisotropy, symm=symm,
+                                          metric=str(self.distance).lower())
+            if self.thresh > 0 or self.decay is None:
+                # new cells (meld_amd/metric_knn.py: cross_kernel_rows): the cells in the caller's order (a reference), the metric's
+                # code, the model of the reduction, the kernel's parameters in the metric's own units
+                attach_extension_state(G, X, X.shape[1] if n_features_in is None else n_features_in, project, None, knn=int(self.knn),
+                                       decay=float("inf") if self.decay is None else float(self.decay), thresh=self.thresh,
+                                       metric=METRICS[str(self.distance).lower()], model=model)
+            return G
         # (the metric enters through the data: cosine = the euclidean graph of the unit rows with the decay doubled)
         X, decay_m, bw_to_metric = metric_front_end(X, self.distance, self.decay)
         bw_opts = {k: opts[k] for k in ("bandwidth", "bandwidth_scale", "knn_max") if opts.get(k) is not None}
@@ -290,7 +304,7 @@ class MELD(GraphEstimator):
         row_fn = None if distance in ("euclidean", "l2", "sqeuclidean") else (lambda Q, m=distance: metric_front_end(Q, m, None)[0])
         attach_extension_state(G, X, X.shape[1] if n_features_in is None else n_features_in, project, row_fn, knn=int(self.knn),
                                decay=float("inf") if decay_m is None else decay_m, thresh=self.thresh, bandwidth=bw_opts.get("bandwidth"),
-                               bandwidth_scale=bw_opts.get("bandwidth_scale"), knn_max=bw_opts.get("knn_max"), ksel=opts.get("ksel"))
+                               bandwidth_scale=bw_opts.get("bandwidth_scale"), knn_max=bw_opts.get("knn_max"), ksel=opts.get("ksel"), model=model)
         # n_landmark (reference meld/meld.py:105,118 forwards it to graphtools): a graphtools LandmarkGraph has the
         # same kernel, weights and Laplacian as the plain kNN graph -- the landmark operator is a lazily built extra
         # (`landmark_op`, `transitions`, `interpolate`) that MELD's filter never touches -- so the densities do not
