@@ -29,7 +29,10 @@ import pandas as pd
 import torch
 import torch.distributed as dist
 
-from .graph import DeviceGraph, resolve_graph_params
+from .graph import DeviceGraph, metric_front_end, resolve_graph_params
+from .graph_plan import plan_graph, plan_reduction
+from .mnn import build_mnn_graph
+from .sparse import reduce_data
 
 __all__ = ["Comm", "shard_range", "build_sharded_graph", "shard_of_graph", "fit_transform_sharded"]
 
@@ -335,49 +338,40 @@ def fit_transform_sharded(op, X, sample_labels, ops=None, comm=None):
     if not isinstance(X, torch.Tensor):
         X = torch.from_numpy(np.ascontiguousarray(np.asarray(getattr(X, "values", X)), dtype=np.float64))
     X = X.to(device=ops.device, dtype=torch.float64).contiguous()
-    # Graphs the row-sharded BUILDER does not build itself -- graphtools' bandwidth / bandwidth_scale / knn_max / kernel_symm / theta,
-    # the dense "exact" graph of thresh = 0, precomputed matrices, the manhattan / chebyshev metrics, knn > 126 -- are built whole on
-    # every rank by the single-GPU builder (``op.fit``: the same front end, the same refusals), and the FILTER is sharded: every rank
-    # keeps its rows (``shard_of_graph``), as for ``sample_idx`` below.  (n_landmark: accepted, the filter never uses the operator.)
+    # Graphs the row-sharded BUILDER does not build itself -- every builder of ``graph_plan.plan_graph`` but "knn", and "knn" with
+    # graphtools' bandwidth / bandwidth_scale / knn_max / kernel_symm / theta -- are built whole on every rank by the single-GPU builder
+    # (``op.fit``: the same plan, the same refusals), and the FILTER is sharded: every rank keeps its rows (``shard_of_graph``), as for
+    # ``sample_idx`` below.  (n_landmark: accepted, the filter never uses the operator.)
     replicated = [k for k in op.kwargs if k not in ("ksel", "sample_idx")]
-    dense_kind = (op.thresh == 0 and op.decay is not None) or str(op.distance).lower().startswith("precomputed") \
-        or str(op.distance).lower() in ("manhattan", "cityblock", "l1", "chebyshev") or min(int(op.knn), int(X.shape[0]) - 2) > 126
-    if (replicated or dense_kind) and op.kwargs.get("sample_idx") is None:
+    if op.kwargs.get("sample_idx") is None and (replicated or plan_graph(
+            tuple(X.shape), sparse_input=False, knn=op.knn, decay=op.decay, thresh=op.thresh, distance=op.distance, n_pca=op.n_pca,
+            opts=op.kwargs).builder != "knn"):
         if not X.is_cuda:
             raise NotImplementedError("graph options {} on the row-sharded driver need the single-GPU builder on every rank (a GPU)".format(sorted(replicated)))
         op.fit(X)
         op.graph = shard_of_graph(op.graph, ops, comm)
         return op.transform(sample_labels)
-    decay = float("inf") if op.decay is None else op.decay  # None: graphtools' unweighted kNN graph = a 0 / 1 kernel
-    # the same front end as the single-GPU path (MELD._build_graph): reject NaN / infinity, and build the
-    # graph on the PCA scores when n_pca < min(X.shape) (graphtools' Data._reduce_data; the reference's
-    # default n_pca=100 triggers it on wide data).  Every rank holds all of X and computes the same
-    # deterministic projection, so no communication is needed.
+    # the same front end as the single-GPU path (MELD._build_graph): reject NaN / infinity, and build the graph on the PCA scores
+    # where the plan reduces (the reference's default n_pca=100 triggers it on wide data).  Every rank holds all of X and computes
+    # the same deterministic projection, so no communication is needed.
     if X.dim() != 2:
         raise ValueError("Expected a 2D data matrix, got shape {}".format(tuple(X.shape)))
     # (one pass: a NaN or an infinity anywhere makes its column sum non-finite; isfinite(X).all() is three)
     if not bool(torch.isfinite(X.sum(dim=0)).all()) and not bool(torch.isfinite(X).all()):
         raise ValueError("Input data contains NaN or infinity")
-    op.data_nu = None
-    if op.n_pca is not None and op.n_pca < min(tuple(X.shape)):
-        from .pca import pca_project
-
-        X = pca_project(X, op.n_pca, seed=42 if op.random_state is None else int(op.random_state)).contiguous()
-        op.data_nu = X
-    from .graph import metric_front_end
-
+    reduction = plan_reduction(tuple(X.shape), False, op.distance, op.n_pca)
+    X = reduce_data(X, reduction, op.n_pca, op.random_state).scores
+    op.data_nu = X if reduction else None
     # (cosine = the euclidean graph of the unit rows with the decay doubled: MELD._build_graph; every rank normalises all of X)
     op.X = X
     X, decay_m, bw_to_metric = metric_front_end(X, op.distance, op.decay)
-    decay = float("inf") if decay_m is None else decay_m
+    decay = float("inf") if decay_m is None else decay_m  # None: graphtools' unweighted kNN graph = a 0 / 1 kernel
     # (the label factorisation of transform starts under this rank's candidate search, as on one GPU)
     finish = op._prefactor_under_search(sample_labels, eligible=X.is_cuda) if hasattr(op, "_prefactor_under_search") else (lambda publish=True: None)
     try:
         if op.kwargs.get("sample_idx") is not None:
             # MNN graph (reference test/test_meld.py:31-40 forwards sample_idx to graphtools): its blocks between samples do not
             # follow the row shards, so every rank builds it whole -- the single-GPU builder -- and keeps its rows
-            from .mnn import build_mnn_graph
-
             full = build_mnn_graph(X, op.kwargs["sample_idx"], knn=op.knn, decay=decay, thresh=op.thresh, anisotropy=op.anisotropy,
                                    ksel=op.kwargs.get("ksel"))
             op.graph = shard_of_graph(full, ops, comm)

@@ -58,6 +58,8 @@ def attach_extension_state(G, X, n_features_in, project, row_fn, knn, decay, thr
 
 def refusal(G):
     """Why this graph cannot be extended (a string), or None."""
+    from .metric_knn import METRICS
+
     info = getattr(G, "info", None) or {}
     if G.n_rows != G.N or getattr(G, "comm", None) is not None:
         return "a row-sharded graph cannot be extended to new cells (every rank holds a slice of the kernel only)"
@@ -66,7 +68,7 @@ def refusal(G):
     if info.get("graph") == "mnn":
         return "an MNN graph (sample_idx) cannot be extended to new cells: a new cell belongs to no sample"
     l1 = getattr(getattr(G, "_extend_state", None), "metric", None) is not None  # (an L1 / L-inf graph that kept its cells)
-    if not l1 and (info.get("route") == "metric_knn" or info.get("metric") in ("manhattan", "cityblock", "l1", "chebyshev")):
+    if not l1 and (info.get("route") == "metric_knn" or info.get("metric") in METRICS):
         return "the L1 / L-inf graphs (distance={!r}) cannot be extended to new cells: the search between two point sets is euclidean".format(info.get("metric"))
     if not l1 and info.get("dense"):
         return ("a dense graph (thresh=0, a precomputed matrix, or a kernel evaluated densely) cannot be extended to new cells: "

@@ -20,8 +20,15 @@ import pandas as pd
 import torch
 
 from . import filter as _filter
+from . import sparse as _sparse
 from . import utils
+from .dense import build_dense_graph, build_dense_knn_graph, build_dense_mnn_graph, build_precomputed_graph
 from .estimator import GraphEstimator, attribute, check_in, check_int, check_positive
+from .extend import attach_extension_state
+from .graph import HipOps, build_knn_graph, metric_front_end
+from .graph_plan import check_options, plan_graph
+from .metric_knn import build_metric_knn_graph
+from .mnn import build_mnn_graph
 
 __all__ = ["MELD"]
 
@@ -125,192 +132,92 @@ class MELD(GraphEstimator):
         return super().set_params(**params)
 
     # -- graph construction (replaces graphtools.Graph(...), reference meld/meld.py:117-118,273) ----
-    def _build_graph(self, data, **kwargs):
-        import torch
-
-        from .graph import build_knn_graph
-
-        opts = dict(self.kwargs)
-        opts.update(kwargs)
-        unsupported = [k for k in opts if k not in ("ksel", "profile", "sample_idx", "bandwidth", "bandwidth_scale", "knn_max", "kernel_symm", "theta")]
-        if unsupported:
-            raise NotImplementedError(
-                "graph options {} are not implemented by the MI355X graph builder".format(sorted(unsupported))
-            )
-        # graphtools' kernel_symm / theta (how K and K^T combine; "+" = (K + K^T) / 2 is the default the reference runs with)
-        from .graph import symm_code
-
-        symm = symm_code(opts.get("kernel_symm", "+"), opts.get("theta"))
-        if symm[0] != 0 and opts.get("sample_idx") is not None:
-            raise NotImplementedError("kernel_symm other than '+' with sample_idx (MNN graph) is not implemented")
-        if not torch.cuda.is_available():
-            raise RuntimeError("meld_amd needs a ROCm GPU (MI355X); there is no CPU fallback")
-        from . import sparse as _sparse
-
-        svd_scores = None
-        project = n_features_in = model = None  # (kept on the graph for new cells: meld_amd/extend.py)
-        if _sparse.is_sparse_input(data):
-            # sparse input (meld_amd/sparse.py): graphtools reduces it with an UNCENTRED truncated SVD where it reduces at all
-            # (Data._reduce_data); without a reduction, and for precomputed matrices, it is densified on the device and takes
-            # the dense path below
-            A = _sparse.DeviceCSR.from_input(data)
-            if (self.n_pca is not None and self.n_pca < min(A.shape)) and not str(self.distance).lower().startswith("precomputed"):
-                self._log("Calculating truncated SVD ({} components)...".format(self.n_pca))
-                svd_scores, svd_v = _sparse.truncated_svd_project(A, self.n_pca, seed=42 if self.random_state is None else int(self.random_state),
-                                                                  return_model=True)
-                project = lambda Q, V=svd_v: Q @ V  # noqa: E731  (graphtools' TruncatedSVD: uncentred)
-                model = dict(kind="svd", V=svd_v)
-                n_features_in = int(A.shape[1])
-                data = svd_scores
-            else:
-                data = A.to_dense()
-            del A
-        if isinstance(data, torch.Tensor):
-            X = data.to(device="cuda", dtype=torch.float64)
-        else:
-            X = torch.from_numpy(data).to("cuda")
-            if X.dtype != torch.float64:
-                X = X.to(torch.float64)  # (float32 input: widened here, after the copy)
-        X_in = X
-        # (one pass: a NaN or an infinity anywhere makes its column sum non-finite; isfinite(X).all() is three.  The pass is the
-        # builder's own -- sums, minima, maxima of the columns, meld_col_stats_f64 -- and its results are handed on to it)
-        col_stats = ops0 = None
+    @staticmethod
+    def _finite_stats(X):
+        """Rejects NaN / infinity in one pass (anywhere in a column, they make its sum non-finite; isfinite(X).all() is three).
+        Where the pass can be the builder's own -- sums, minima, maxima of the columns, meld_col_stats_f64 -- returns
+        (the HipOps that ran it, its results) for the builder, else (None, None)."""
+        ops = col_stats = None
         if X.dim() == 2 and X.shape[1] <= 256 and X.shape[0] > 0 and X.is_contiguous():
-            from .graph import HipOps
-
-            ops0 = HipOps(X.device)
-            col_stats = ops0.col_stats(X)
+            ops = HipOps(X.device)
+            col_stats = ops.col_stats(X)
             finite = bool(torch.isfinite(col_stats[0]).all())
         else:
             finite = bool(torch.isfinite(X.sum(dim=0)).all())
         if not finite and not bool(torch.isfinite(X).all()):
             raise ValueError("Input data contains NaN or infinity")
-        self.data_nu = svd_scores
-        if str(self.distance).lower().startswith("precomputed"):
-            # [UPSTREAM graphtools GraphEstimator._parse_input]: the input IS a square matrix of pairwise distances or
-            # affinities ("precomputed": told apart by its first diagonal entry, 0 = distances); no PCA, dense graph
-            from .dense import build_precomputed_graph
+        return ops, col_stats
 
-            if any(opts.get(k) is not None for k in ("sample_idx", "bandwidth", "bandwidth_scale", "knn_max")):
-                raise NotImplementedError("sample_idx / bandwidth options with a precomputed matrix are not implemented")
-            kind = str(self.distance).lower()[len("precomputed"):].lstrip("_")
-            if X.dim() != 2 or X.shape[0] != X.shape[1]:
-                raise ValueError("Precomputed {} must be a square matrix. {} was given".format(kind or "matrix", tuple(X.shape)))
-            if not kind:
-                kind = "distance" if float(X[0, 0]) == 0.0 else "affinity"
-            return build_precomputed_graph(X, kind, knn=self.knn, decay=self.decay, thresh=self.thresh, anisotropy=self.anisotropy, symm=symm)
-        if svd_scores is None and self.n_pca is not None and self.n_pca < min(tuple(X.shape)):
-            # graphtools reduces the data with PCA first (Data._reduce_data) and builds the graph on
-            # the scores; here: exact top-n_pca subspace on the device (meld_amd/pca.py)
-            from .pca import pca_project
-
-            self._log("Calculating PCA ({} components)...".format(self.n_pca))
-            n_features_in = int(X.shape[1])
-            X, pca_mean, pca_v = pca_project(X, self.n_pca, seed=42 if self.random_state is None else int(self.random_state), return_model=True)
-            project = lambda Q, mean=pca_mean, V=pca_v: (Q - mean) @ V  # noqa: E731
-            model = dict(kind="pca", mean=pca_mean, V=pca_v)
-            self.data_nu = X
-        from .graph import metric_front_end
-
-        if str(self.distance).lower() in ("manhattan", "cityblock", "l1", "chebyshev"):
-            # metrics that are no function of the euclidean distance of transformed rows: the matrix pipe's search does not apply;
-            # the same kernel on library pairwise distances, densely, up to DENSE_MAX_N cells, and beyond that the exact L1 / L-inf
-            # search of meld_amd.metric_knn
-            from .dense import build_dense_knn_graph
-            from .metric_knn import build_metric_knn_graph, metric_route
-
-            try:
-                route = metric_route(int(X.shape[0]), int(X.shape[1]), self.knn, self.decay, self.thresh, opts)
-            except NotImplementedError:
-                raise NotImplementedError("distance={!r} is implemented for the plain alpha-decay / unweighted kNN graph only".format(self.distance)) from None
-            from .extend import attach_extension_state
-            from .metric_knn import METRICS
-
-            if route == "metric_knn":
-                G = build_metric_knn_graph(X, self.knn, self.decay, self.thresh, self.anisotropy, str(self.distance).lower(),
-                                           kernel_symm=opts.get("kernel_symm", "+"), theta=opts.get("theta"), ksel=opts.get("ksel"),
-                                           profile=bool(opts.get("profile", False)), ops=ops0)
-            else:
-                G = build_dense_knn_graph(X, self.knn, self.decay, self.thresh, anisotropy=self.anisotropy, symm=symm,
-                                          metric=str(self.distance).lower())
-            if self.thresh > 0 or self.decay is None:
-                # new cells (meld_amd/metric_knn.py: cross_kernel_rows): the cells in the caller's order (a reference), the metric's
-                # code, the model of the reduction, the kernel's parameters in the metric's own units
-                attach_extension_state(G, X, X.shape[1] if n_features_in is None else n_features_in, project, None, knn=int(self.knn),
-                                       decay=float("inf") if self.decay is None else float(self.decay), thresh=self.thresh,
-                                       metric=METRICS[str(self.distance).lower()], model=model)
-            return G
-        # (the metric enters through the data: cosine = the euclidean graph of the unit rows with the decay doubled)
-        X, decay_m, bw_to_metric = metric_front_end(X, self.distance, self.decay)
-        bw_opts = {k: opts[k] for k in ("bandwidth", "bandwidth_scale", "knn_max") if opts.get(k) is not None}
-        dense_exact = self.thresh == 0 and self.decay is not None
-        if self.decay is None and opts.get("sample_idx") is None:
-            # [UPSTREAM graphtools kNNGraph.build_kernel_to_data]: without alpha decay the kernel is the connectivity of the knn + 1
-            # nearest cells and the function returns before it looks at bandwidth, bandwidth_scale or knn_max: accepted, no effect
-            bw_opts = {}
-        if bw_opts and (opts.get("sample_idx") is not None or (dense_exact and "knn_max" in bw_opts)
-                        or str(self.distance).lower() not in ("euclidean", "l2")):
-            raise NotImplementedError("bandwidth / bandwidth_scale / knn_max are implemented for the euclidean alpha-decay graphs only -- the sparse kNN "
-                                      "graph, and (without knn_max) the dense graph of thresh=0 -- not with sample_idx or another distance")
-        if callable(bw_opts.get("bandwidth")) and not dense_exact:
-            # [UPSTREAM graphtools kNNGraph.__init__]: "Callable bandwidth is only supported by graphtools.graphs.TraditionalGraph."
-            raise NotImplementedError("Callable bandwidth is only supported by the dense graph of thresh=0 (graphtools.graphs.TraditionalGraph)")
-        if opts.get("sample_idx") is not None:
-            # graphtools builds its MNN graph when sample_idx is forwarded (reference test/test_meld.py:34)
-            if self.thresh == 0 and self.decay is not None:  # "exact" subgraphs: the dense route
-                from .dense import build_dense_mnn_graph
-
-                G = build_dense_mnn_graph(X, opts["sample_idx"], knn=self.knn, decay=decay_m, anisotropy=self.anisotropy)
-                G.bandwidth_to_metric = bw_to_metric
-                return G
-            from .mnn import build_mnn_graph
-
-            G = build_mnn_graph(
-                X, opts["sample_idx"], knn=self.knn, decay=float("inf") if decay_m is None else decay_m,
-                thresh=self.thresh, anisotropy=self.anisotropy, ksel=opts.get("ksel"),
+    def _build_graph(self, data, **kwargs):
+        """Follows ``graph_plan.plan_graph``: options, upload and finite check, plan, reduction, metric
+        front end, the plan's builder, and one finishing stage for what every graph carries."""
+        opts = dict(self.kwargs)
+        opts.update(kwargs)
+        check_options(opts)
+        if not torch.cuda.is_available():
+            raise RuntimeError("meld_amd needs a ROCm GPU (MI355X); there is no CPU fallback")
+        sparse_input = _sparse.is_sparse_input(data)
+        if sparse_input:
+            # sparse input (meld_amd/sparse.py) stays CSR on the device up to its reduction; its values are checked on upload
+            # and the matrix the builder sees -- scores, or densified where nothing reduces it -- below
+            data = _sparse.DeviceCSR.from_input(data)
+        elif isinstance(data, torch.Tensor):
+            data = data.to(device="cuda", dtype=torch.float64)
+        else:
+            data = torch.from_numpy(data).to("cuda")
+            if data.dtype != torch.float64:
+                data = data.to(torch.float64)  # (float32 input: widened here, after the copy)
+        ops0, col_stats = (None, None) if sparse_input else self._finite_stats(data)
+        plan = plan_graph(tuple(data.shape), sparse_input=sparse_input, knn=self.knn, decay=self.decay, thresh=self.thresh,
+                          distance=self.distance, n_pca=self.n_pca, opts=opts)
+        red = _sparse.reduce_data(data, plan.reduction, self.n_pca, self.random_state, log=self._log)
+        X_in = X = red.scores
+        del data  # (a device CSR matrix has served its purpose)
+        if sparse_input:
+            ops0, col_stats = self._finite_stats(X)
+        self.data_nu = X if plan.reduction else None
+        decay_m, bw_to_metric = self.decay, None
+        if plan.front_end:
+            X, decay_m, bw_to_metric = metric_front_end(X, plan.distance, self.decay)
+        decay_inf = float("inf") if decay_m is None else decay_m  # None: the unweighted kNN graph = a 0 / 1 kernel
+        bw, ksel = plan.bw_opts, opts.get("ksel")
+        if plan.builder == "precomputed":
+            kind = plan.precomputed_kind or ("distance" if float(X[0, 0]) == 0.0 else "affinity")
+            G = build_precomputed_graph(X, kind, knn=self.knn, decay=self.decay, thresh=self.thresh, anisotropy=self.anisotropy, symm=plan.symm)
+        elif plan.builder == "metric_knn":
+            G = build_metric_knn_graph(X, self.knn, self.decay, self.thresh, self.anisotropy, plan.distance,
+                                       kernel_symm=opts.get("kernel_symm", "+"), theta=opts.get("theta"), ksel=ksel,
+                                       profile=bool(opts.get("profile", False)), ops=ops0)
+        elif plan.builder in ("dense_metric", "dense_knn"):
+            G = build_dense_knn_graph(X, self.knn, decay_m, self.thresh, anisotropy=self.anisotropy, symm=plan.symm,
+                                      metric=plan.distance if plan.metric else "euclidean")
+        elif plan.builder == "dense_mnn":
+            G = build_dense_mnn_graph(X, opts["sample_idx"], knn=self.knn, decay=decay_m, anisotropy=self.anisotropy)
+        elif plan.builder == "mnn":
+            G = build_mnn_graph(X, opts["sample_idx"], knn=self.knn, decay=decay_inf, thresh=self.thresh, anisotropy=self.anisotropy, ksel=ksel)
+        elif plan.builder == "dense_exact":
+            G = build_dense_graph(X, knn=self.knn, decay=decay_m, anisotropy=self.anisotropy, symm=plan.symm,
+                                  bandwidth=bw.get("bandwidth"), bandwidth_scale=bw.get("bandwidth_scale", 1.0))
+        else:
+            G = build_knn_graph(
+                X, knn=self.knn, decay=decay_inf, thresh=self.thresh, anisotropy=self.anisotropy,
+                ksel=ksel, profile=bool(opts.get("profile", False)), **bw,
+                # (the column statistics are those of the cells the graph is built on: not after a reduction / a metric front end)
+                col_stats=col_stats if (plan.reduction is None and X is X_in) else None,
+                kernel_symm=opts.get("kernel_symm", "+"), theta=opts.get("theta"), ops=ops0,
             )
-            G.bandwidth_to_metric = bw_to_metric
-            return G
-        # ([UPSTREAM graphtools api.Graph]: decay=None selects the kNN graph -- unweighted connectivity -- BEFORE thresh is looked
-        # at; only an alpha-decay kernel with thresh = 0 is the dense "exact" graph)
-        if self.thresh == 0 and self.decay is not None:
-            from .dense import build_dense_graph
-
-            G = build_dense_graph(X, knn=self.knn, decay=decay_m, anisotropy=self.anisotropy, symm=symm,
-                                  bandwidth=bw_opts.get("bandwidth"), bandwidth_scale=bw_opts.get("bandwidth_scale", 1.0))
-            G.bandwidth_to_metric = bw_to_metric
-            return G
-        if min(int(self.knn), int(X.shape[0]) - 2) > 126 and not bw_opts:
-            # beyond the candidate lists of the search kernel (128 entries): the same kernel evaluated densely, small N only
-            from .dense import build_dense_knn_graph
-
-            G = build_dense_knn_graph(X, self.knn, decay_m, self.thresh, anisotropy=self.anisotropy, symm=symm)
-            G.bandwidth_to_metric = bw_to_metric
-            return G
-        G = build_knn_graph(
-            X, knn=self.knn, decay=float("inf") if decay_m is None else decay_m,  # None: unweighted kNN graph
-            thresh=self.thresh, anisotropy=self.anisotropy,
-            ksel=opts.get("ksel"), profile=bool(opts.get("profile", False)), **bw_opts,
-            # (the column statistics are those of the cells the graph is built on: not after a PCA / a metric front end)
-            col_stats=col_stats if (self.data_nu is None and X is X_in) else None,
-            kernel_symm=opts.get("kernel_symm", "+"), theta=opts.get("theta"), ops=ops0,
-        )
         G.bandwidth_to_metric = bw_to_metric
-        # what new cells need (DeviceGraph.build_kernel_to_data / extend_to_data / interpolate): the matrix the search saw, in the
-        # caller's order (a reference: the graph pins it), the model that maps a raw cell to it, the kernel's parameters
-        from .extend import attach_extension_state
-
-        distance = str(self.distance).lower()
-        row_fn = None if distance in ("euclidean", "l2", "sqeuclidean") else (lambda Q, m=distance: metric_front_end(Q, m, None)[0])
-        attach_extension_state(G, X, X.shape[1] if n_features_in is None else n_features_in, project, row_fn, knn=int(self.knn),
-                               decay=float("inf") if decay_m is None else decay_m, thresh=self.thresh, bandwidth=bw_opts.get("bandwidth"),
-                               bandwidth_scale=bw_opts.get("bandwidth_scale"), knn_max=bw_opts.get("knn_max"), ksel=opts.get("ksel"), model=model)
-        # n_landmark (reference meld/meld.py:105,118 forwards it to graphtools): a graphtools LandmarkGraph has the
-        # same kernel, weights and Laplacian as the plain kNN graph -- the landmark operator is a lazily built extra
-        # (`landmark_op`, `transitions`, `interpolate`) that MELD's filter never touches -- so the densities do not
-        # depend on it.  The parameter is accepted and recorded; asking the graph for the landmark operator itself is
-        # what is not implemented.
+        # n_landmark (reference meld/meld.py:105,118 forwards it to graphtools): a graphtools LandmarkGraph has the same kernel,
+        # weights and Laplacian as the plain graph -- the landmark operator is a lazily built extra that MELD's filter never
+        # touches -- so the parameter is accepted and recorded; asking the graph for the operator itself is what is not implemented
         G.n_landmark = self.n_landmark
+        if plan.keeps_cells:
+            # what new cells need (meld_amd/extend.py): the matrix the search saw, in the caller's order (a reference: the graph
+            # pins it), the model that maps a raw cell to it, the kernel's parameters in the units of the search
+            row_fn = (lambda Q, m=plan.distance: metric_front_end(Q, m, None)[0]) if plan.transforms_rows else None
+            attach_extension_state(G, X, red.n_features_in, red.project, row_fn, knn=int(self.knn), decay=decay_inf, thresh=self.thresh,
+                                   bandwidth=bw.get("bandwidth"), bandwidth_scale=bw.get("bandwidth_scale"), knn_max=bw.get("knn_max"),
+                                   ksel=None if plan.metric else ksel, metric=plan.metric, model=red.model)
         return G
 
     # -- indicators (reference meld/meld.py:143-191) ------------------------------------------------

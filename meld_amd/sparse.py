@@ -11,9 +11,12 @@ data gets a centred PCA.  This module is that front end without a dense copy of 
   the affinity build: rows ascending inside each column, so products with it are deterministic);
 * ``truncated_svd_project``: the exact top-k right singular subspace through the Gram matrix X^T X for G <= pca.EXACT_MAX
   genes, the randomized range finder of ``pca.py`` otherwise; every product against X is ``meld_csr_spmm_f64``
-  (csrc/csr_dense.hip).
+  (csrc/csr_dense.hip);
+* ``reduce_data``: the one reduction step of the graph build, sparse (this SVD) or dense (``pca.pca_project``).
 """
 from __future__ import annotations
+
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -21,7 +24,7 @@ import torch
 from . import pca as _pca
 from ._lib import check, get_lib, ptr
 
-__all__ = ["is_sparse_input", "to_host_csr", "DeviceCSR", "truncated_svd_project"]
+__all__ = ["is_sparse_input", "to_host_csr", "DeviceCSR", "truncated_svd_project", "reduce_data"]
 
 
 def _scipy_sparse():
@@ -282,3 +285,29 @@ def truncated_svd_project(A, k, seed=42, return_model=False):
     if return_model:
         return Y, V
     return Y
+
+
+def reduce_data(data, kind, n_components, random_state=None, log=None):
+    """The reduction the graph is built on ([UPSTREAM graphtools ``Data._reduce_data``], chosen by ``graph_plan.plan_reduction``):
+    ``kind="svd"``: the uncentred truncated SVD of a ``DeviceCSR``; ``"pca"``: the exact top-``n_components`` subspace of a dense
+    device matrix (meld_amd/pca.py); ``None``: the data as they are, a ``DeviceCSR`` densified on the device.  Returns
+    ``scores``, ``project`` (raw device rows of new cells -> their scores, None without a reduction), ``model`` (its tensors)
+    and ``n_features_in``."""
+    seed = 42 if random_state is None else int(random_state)
+    project = model = None
+    n_features_in = int(data.shape[1])
+    if kind == "svd":
+        if log is not None:
+            log("Calculating truncated SVD ({} components)...".format(n_components))
+        data, V = truncated_svd_project(data, n_components, seed=seed, return_model=True)
+        project = lambda Q, V=V: Q @ V  # noqa: E731  (graphtools' TruncatedSVD: uncentred)
+        model = dict(kind="svd", V=V)
+    elif kind == "pca":
+        if log is not None:
+            log("Calculating PCA ({} components)...".format(n_components))
+        data, mean, V = _pca.pca_project(data, n_components, seed=seed, return_model=True)
+        project = lambda Q, mean=mean, V=V: (Q - mean) @ V  # noqa: E731
+        model = dict(kind="pca", mean=mean, V=V)
+    elif isinstance(data, DeviceCSR):
+        data = data.to_dense()
+    return SimpleNamespace(scores=data, project=project, model=model, n_features_in=n_features_in)
