@@ -169,8 +169,16 @@ int meld_knn16_bounds_from_spheres(const double* X, int64_t N, int d, const doub
  * identical).  The norm pieces live in the hi plane and are exact in either mode. */
 /* meld_knn16_prepare for a search between two point sets (the blocks between two samples of graphtools' MNN kernel,
  * reached through reference meld/meld.py:117-118 with sample_idx=, test/test_meld.py:34): X holds n_total rows, the
- * references are rows [0, n_refs), the queries a range of the rest.  Scaling over all rows; norm2 / norm2_max cover the
- * references only (the caller merges the queries' norms from Qn). */
+ * references are rows [0, n_refs), the queries a range of the rest.  Scaling (and mean) over all n_total rows.  Outputs and
+ * their units:
+ *   Rt16, Q16     the operands of meld_knn16_prepare: centred coordinates times scale_info[0], fp16 hi / lo planes (scaled units);
+ *   Qn            [roundup(q_count, BQ)] the queries' |x~|^2 in the search's SCALED units (input units * scale_info[0]^2);
+ *   norm2         [n_total] |x - mean|^2 in INPUT units: rows [0, n_refs) for the references and rows [q_begin, q_begin + q_count)
+ *                 for the queries (norm2[q_begin + i] * scale_info[0]^2 == Qn[i]); rows of neither range are not written;
+ *   norm2_max     [1] the maximum of those norms over the references AND the queries, input units;
+ *   scale_info    [4] {s = 1 / absmax, 1 / s^2, absmax = max |x - mean| over all entries of the n_total rows (input units), 0}.
+ * meld_knn_refine, the radius cut of meld_knn16_topk and meld_knn16_research_thresholds read norm2 / norm2_max as input-unit
+ * quantities for queries and references alike (tests/test_gpu_cross_search.py pins this). */
 int meld_knn16_prepare_cross(const double* X, int64_t n_refs, int64_t n_total, int d, const double* mean, int64_t q_begin,
                              int64_t q_count, void* Rt16, void* Q16, float* Qn, float* norm2, float* norm2_max,
                              float* scale_info, meld_stream_t stream);

@@ -1919,6 +1919,24 @@ __global__ __launch_bounds__(256) void prepare16_kernel(const double* __restrict
   }
 }
 
+// Search between two point sets: the queries are not among the references, so prepare16_kernel<true> never sees them.  Their
+// |x - mean|^2 in INPUT units go to their own rows of norm2 (Qn[q] / s^2: the product a reference with the same coordinates gets
+// from prepare16_kernel<true>, bit for bit) and norm2_max is raised to cover them -- refine's allowance, the radius cut and the
+// re-search thresholds read both as input-unit quantities.  Qn itself stays in the search's scaled units.
+__global__ __launch_bounds__(256) void cross_query_norms_kernel(const float* __restrict__ Qn, const float* __restrict__ scale_info,
+                                                                int64_t q_begin, int64_t q_count, float* __restrict__ norm2,
+                                                                float* __restrict__ norm2_max) {
+  const int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  float n_orig = 0.0f;
+  if (q < q_count) {
+    n_orig = Qn[q] * scale_info[1];
+    norm2[q_begin + q] = n_orig;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) n_orig = fmaxf(n_orig, __shfl_xor(n_orig, off, 64));
+  if ((threadIdx.x & 63) == 0) atomicMax(reinterpret_cast<int*>(norm2_max), __float_as_int(n_orig));
+}
+
 // Queries = all the references (every single-GPU build): ONE read of a tile's 64 rows gives the tile in Rt layout, the same rows
 // in Q layout with Qn, norm2 and norm2_max, and the tile's sphere -- prepare16_kernel<true>, prepare16_kernel<false> and
 // tile_spheres_kernel on the same rows, each value from the same operations in the same order (tests/test_gpu_fused_operands.py
@@ -2335,8 +2353,9 @@ extern "C" int meld_knn16_prepare_fused(const double* X, int64_t N, int d, const
 
 // The same for a search between two point sets (the blocks of graphtools' MNN kernel between two samples): X holds
 // n_total rows, the references are its rows [0, n_refs), the queries any range of it (the caller puts the query set
-// behind the references).  Scaling over all n_total rows; norm2 / norm2_max cover the references (the caller adds the
-// queries' from Qn).
+// behind the references).  Scaling over all n_total rows.  Units of the outputs: norm2 (n_total entries) holds |x - mean|^2 in INPUT
+// units for the references [0, n_refs) and for the queries [q_begin, q_begin + q_count) (other rows are not written), norm2_max
+// their maximum over both sets, input units; Qn the queries' norms in the search's SCALED units (input * scale_info[0]^2).
 extern "C" int meld_knn16_prepare_cross(const double* X, int64_t n_refs, int64_t n_total, int d, const double* mean,
                                         int64_t q_begin, int64_t q_count, void* Rt16, void* Q16, float* Qn, float* norm2,
                                         float* norm2_max, float* scale_info, meld_stream_t stream) {
@@ -2356,6 +2375,8 @@ extern "C" int meld_knn16_prepare_cross(const double* X, int64_t n_refs, int64_t
   const int64_t q_pad = ceil_div(q_count, K16_BQ) * K16_BQ;
   hipLaunchKernelGGL((prepare16_kernel<false>), dim3((unsigned)(q_pad / K16_TS)), dim3(256), 0, st, X, n_total, d, mean, scale_info,
                      KB, q_begin, q_count, (const int*)nullptr, reinterpret_cast<_Float16*>(Q16), Qn, (float*)nullptr, k16_dA(d, KB));
+  hipLaunchKernelGGL(cross_query_norms_kernel, dim3((unsigned)ceil_div(q_count, 256)), dim3(256), 0, st, Qn, scale_info, q_begin, q_count,
+                     norm2, norm2_max);
   MELD_LAUNCH_CHECK("meld_knn16_prepare_cross");
   return MELD_OK;
 }

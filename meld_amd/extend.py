@@ -245,13 +245,13 @@ def _stack_scaled(ops, Xr, Qc):
     """The stacked matrix [fitted; new] of one search call, multiplied by a power of two so that its largest centred coordinate
     lies in (1/2, 1), and its column statistics.
 
-    Why: the search between two point sets takes the per-row part of its error allowance for a QUERY from the query's norm in
-    the search's own scaled units (``Qn`` of ``meld_knn16_prepare_cross``: the data times 1 / absmax), for a reference from its
-    norm in input units.  For cells whose coordinates exceed 1 the queries' allowance is then too small by that factor, and a
-    new cell far from the centre of the data can be certified with neighbours missing (seen on the fixture: the rows of the far
-    outliers lost most of their entries).  With absmax in (1/2, 1) the scaled norm is never below the true one (at most 4 times it:
-    a few more rows take the exact sweep).  The kernel only sees distances as the ratio dist / bandwidth and a power of two
-    scales every coordinate exactly, so the values are those of the unscaled cells, bit for bit."""
+    No longer needed for correctness: ``meld_knn16_prepare_cross`` now hands the search the queries' norms in input units, as it
+    does the references' (tests/test_gpu_cross_search.py), and certification does not depend on the unit of length.  It was
+    introduced when a query's norm reached the error allowance in the search's scaled units (data / absmax), which for cells
+    with coordinates above 1 made the allowance too small and let a new cell far from the centre be certified with neighbours
+    missing.  Kept because it is harmless and keeps the extension's results as they were: the kernel only sees distances as the
+    ratio dist / bandwidth and a power of two scales every coordinate exactly, so the values are those of the unscaled cells,
+    bit for bit."""
     N, m, d = int(Xr.shape[0]), int(Qc.shape[0]), int(Xr.shape[1])
     Xcat = torch.empty(N + m, d, dtype=torch.float64, device=Xr.device)
     Xcat[:N] = Xr

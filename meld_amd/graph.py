@@ -810,10 +810,9 @@ class HipOps:
         o.scale_info = torch.empty(4, dtype=torch.float32, device=dev)
         tail = (a.q_begin, a.q_count, ptr(o.Rt), ptr(o.Q), ptr(o.Qn), ptr(norm2), ptr(nmax), ptr(o.scale_info), st)
         if a.cross:
+            # (norm2 / nmax come back covering the queries too, in input units: the error bounds speak of the largest norm among ALL
+            # points of the search, and refine reads the query's own norm at its row)
             check(lib.meld_knn16_prepare_cross(ptr(X), a.NR, N, d, ptr(mean), *tail), "meld_knn16_prepare_cross")
-            # the error bounds speak of the largest norm among ALL points of the search, and refine reads the query's own norm at its row
-            norm2[a.q_begin : a.q_begin + a.q_count] = o.Qn[: a.q_count]
-            nmax = torch.maximum(nmax, o.Qn[: a.q_count].max().reshape(1))
         elif plan.fused_operands:
             # queries = all the references: both layouts and the tile spheres (for _step_lists) from one read of every tile
             o.spheres = torch.empty(lib.meld_knn16_bounds_temp_bytes(N, d, a.q_count), dtype=torch.uint8, device=dev)
