@@ -562,6 +562,25 @@ int meld_cheby_step(const meld_laplacian_t* L, int p, const double* x_full, int6
 int meld_cheby_step_wide(const meld_laplacian_t* L, int p, const double* x_full, int64_t x_row_offset, const double* z, double* y,
                          double alpha, double beta, double gamma, meld_stream_t stream);
 
+/* ---- tall-block algebra of the partial Fourier basis (csrc/subspace.hip; the Rayleigh-Ritz step of the Chebyshev-filtered
+ *      subspace iteration that stands for [UPSTREAM pygsp (development line) Graph.compute_fourier_basis(n_eigenvectors=k)]) ----
+ * Tall operands are fp64, row-major [n_rows, m] with a leading dimension ld >= m (in doubles), 1 <= m <= 64; the entries of a row
+ * beyond column m are neither read nor written.  No floating-point atomics: workgroup b < n_blocks sums the rows
+ * [b per, (b + 1) per), per = ceil(n_rows / n_blocks), into part[b] and a second launch adds the partials in workgroup order --
+ * the result is a function of the operands and of n_blocks alone, the same bits every run.  1 <= n_blocks <=
+ * meld_block_max_blocks().
+ *   meld_block_gram_f64:      C[m, m] (row-major, tight) = A^T B;               part: n_blocks * m * m doubles
+ *   meld_block_rotate_f64:    out = A S, S [m, m] row-major, tight, on the device (staged in LDS); out may alias A (then
+ *                             ldo == lda): a row is read whole before it is written
+ *   meld_block_residuals_f64: out[j] = sum_i (LV[i][j] - theta[j] V[i][j])^2;   part: n_blocks * m doubles */
+int meld_block_max_blocks(void);
+int meld_block_gram_f64(const double* A, int64_t lda, const double* B, int64_t ldb, int64_t n_rows, int m, double* part, int n_blocks,
+                        double* C, meld_stream_t stream);
+int meld_block_rotate_f64(const double* A, int64_t lda, const double* S, int64_t n_rows, int m, double* out, int64_t ldo,
+                          meld_stream_t stream);
+int meld_block_residuals_f64(const double* LV, const double* V, int64_t ld, const double* theta, int64_t n_rows, int m, double* part,
+                             int n_blocks, double* out, meld_stream_t stream);
+
 /* r = a * x  (n doubles) -- initialises r = c0/2 * T0 */
 /* Device-resident Lanczos iterations [it_begin, it_begin + n_iter) of L (single GPU: all n_rows rows local), for the lmax
  * estimate ([UPSTREAM pygsp Graph.estimate_lmax], reference meld/filter.py:39).  v0/v1/v2 [n_rows]: the three rotating

@@ -136,6 +136,10 @@ SIGNATURES = {
     "meld_pt_desc_len": (_i64, [_i32]),
     "meld_pt_build": (_i32, [_ptr, _ptr, _ptr, _i64, _i64, _i64, _i32, _ptr, _ptr, _ptr, _ptr]),
     "meld_cheby_step_wide": (_i32, [_ptr, _i32, _ptr, _i64, _ptr, _ptr, _f64, _f64, _f64, _ptr]),
+    "meld_block_max_blocks": (_i32, []),
+    "meld_block_gram_f64": (_i32, [_ptr, _i64, _ptr, _i64, _i64, _i32, _ptr, _i32, _ptr, _ptr]),
+    "meld_block_rotate_f64": (_i32, [_ptr, _i64, _ptr, _i64, _i32, _ptr, _i64, _ptr]),
+    "meld_block_residuals_f64": (_i32, [_ptr, _ptr, _i64, _ptr, _i64, _i32, _ptr, _i32, _ptr, _ptr]),
     "meld_kmeans_max_blocks": (_i32, []),
     "meld_kmeans_assign": (_i32, [_ptr, _i64, _i32, _ptr, _i32, _ptr, _ptr, _ptr, _ptr, _i32, _ptr]),
     "meld_scale_f64": (_i32, [_ptr, _f64, _ptr, _i64, _ptr]),

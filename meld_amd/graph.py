@@ -356,12 +356,24 @@ class DeviceGraph:
 
     FOURIER_MAX_N = 16384
 
-    def compute_fourier_basis(self, recompute=False):
+    def compute_fourier_basis(self, recompute=False, n_eigenvectors=None, tol=1e-6, max_iter=200, seed=0):
         """pygsp's ``compute_fourier_basis``: full eigendecomposition of the combinatorial Laplacian -- ``e`` ascending,
         ``U`` the eigenvectors (columns), both host arrays in the caller's cell order; also sets ``lmax = e[-1]`` like
-        pygsp.  Dense O(N^3) on the device (rocSOLVER ``eigh``), offered up to FOURIER_MAX_N cells."""
+        pygsp.  Dense O(N^3) on the device (rocSOLVER ``eigh``), offered up to FOURIER_MAX_N cells.
+
+        ``n_eigenvectors=k`` ([UPSTREAM pygsp development line]; 1 <= k <= 48): computes and caches the ``k`` smallest
+        eigenpairs only, at any graph size (``meld_amd/spectrum.py``); read them with ``fourier_basis(k)``.  ``U`` / ``e`` /
+        ``lmax`` are not touched by it."""
+        if n_eigenvectors is not None:
+            self.fourier_basis_device(n_eigenvectors, recompute=recompute, tol=tol, max_iter=max_iter, seed=seed)
+            return
         if getattr(self, "_U", None) is not None and not recompute:
             return
+        self._e, self._U = self._dense_fourier()
+        self.lmax = float(self._e[-1])
+
+    def _dense_fourier(self):
+        """``(e, U)`` of the full dense decomposition, host arrays in the caller's order; nothing is stored."""
         if self.n_rows != self.N:
             raise ValueError("the Fourier basis is only defined for an unsharded graph")
         if self.N > self.FOURIER_MAX_N:
@@ -377,8 +389,37 @@ class DeviceGraph:
         inv = self._inv_perm_host()
         if inv is not None:
             U = U[inv]
-        self._e, self._U = e, U
-        self.lmax = float(e[-1])
+        return e, U
+
+    def fourier_basis_device(self, k, recompute=False, tol=1e-6, max_iter=200, seed=0):
+        """The ``k`` smallest eigenpairs of the combinatorial Laplacian as device tensors ``(e [k], U [N, k])``: ``e`` ascending,
+        one row of ``U`` per cell in the caller's order, each column's entry of largest magnitude positive.  1 <= k <= 48;
+        Chebyshev-filtered subspace iteration on the device (``meld_amd/spectrum.py``; up to 128 cells a slice of the dense
+        decomposition), to residuals ``|L u - e u| <= tol * ub`` with ``ub`` a rigorous upper bound of the spectrum; RuntimeError
+        when ``max_iter`` filter applications do not get there.  Computed on first use and kept per ``(k, tol, seed)``, apart
+        from ``U`` / ``e``; ``lmax`` is neither set nor changed."""
+        from . import spectrum
+
+        key = (spectrum.check_k(k), float(tol), int(seed))
+        if self.n_rows != self.N:
+            raise ValueError("the Fourier basis is only defined for an unsharded graph")
+        cache = self.__dict__.setdefault("_partial_fourier", {})
+        if recompute or key not in cache:
+            cache.pop(key, None)
+            e, U, info = spectrum.partial_basis_device(self, key[0], tol=tol, max_iter=max_iter, seed=seed)
+            cache[key] = dict(e=e, U=U, info=info, host=None)
+        self.fourier_partial_info = cache[key]["info"]
+        return cache[key]["e"], cache[key]["U"]
+
+    def fourier_basis(self, k, recompute=False, tol=1e-6, max_iter=200, seed=0):
+        """``fourier_basis_device`` as host fp64 arrays ``(e [k], U [N, k])``."""
+        from . import spectrum
+
+        self.fourier_basis_device(k, recompute=recompute, tol=tol, max_iter=max_iter, seed=seed)
+        kept = self._partial_fourier[(spectrum.check_k(k), float(tol), int(seed))]
+        if kept["host"] is None:
+            kept["host"] = (kept["e"].cpu().numpy(), kept["U"].cpu().numpy())
+        return kept["host"]
 
     @property
     def U(self):
@@ -1449,6 +1490,28 @@ class HipOps:
                                           float(beta), float(gamma), _stream()),
             "meld_cheby_step_wide",
         )
+
+    # tall-block algebra of the partial Fourier basis (csrc/subspace.hip): fp64 row-major blocks [n_rows, m], m <= 64, the
+    # leading dimension taken from the tensor's row stride; per-workgroup partials added in workgroup order (no atomics)
+    def block_n_blocks(self, n_rows):
+        """Workgroups (= partial slots) of the two reductions for ``n_rows`` rows."""
+        return int(min(self.lib.meld_block_max_blocks(), max(1, (int(n_rows) + 63) // 64)))
+
+    def block_gram(self, A, B, n_rows, m, part, n_blocks, C):
+        """``C[m, m] = A^T B`` (``meld_block_gram_f64``); ``part``: ``n_blocks * m * m`` doubles."""
+        check(self.lib.meld_block_gram_f64(ptr(A), int(A.stride(0)), ptr(B), int(B.stride(0)), int(n_rows), int(m), ptr(part), int(n_blocks),
+                                           ptr(C), _stream()), "meld_block_gram_f64")
+
+    def block_rotate(self, A, S, n_rows, m, out):
+        """``out = A S`` for ``S [m, m]`` on the device (``meld_block_rotate_f64``); ``out`` may be ``A``."""
+        check(self.lib.meld_block_rotate_f64(ptr(A), int(A.stride(0)), ptr(S), int(n_rows), int(m), ptr(out), int(out.stride(0)), _stream()),
+              "meld_block_rotate_f64")
+
+    def block_residuals(self, LV, V, theta, n_rows, m, part, n_blocks, out):
+        """``out[j] = sum_i (LV[i, j] - theta[j] V[i, j])^2`` (``meld_block_residuals_f64``); ``part``: ``n_blocks * m`` doubles."""
+        assert LV.stride(0) == V.stride(0)
+        check(self.lib.meld_block_residuals_f64(ptr(LV), ptr(V), int(V.stride(0)), ptr(theta), int(n_rows), int(m), ptr(part), int(n_blocks),
+                                                ptr(out), _stream()), "meld_block_residuals_f64")
 
     @staticmethod
     def _slice_begin(G, comm):
