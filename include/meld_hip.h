@@ -271,6 +271,17 @@ int meld_knn16_topk_listed_partial(const void* Q16, const float* Qn, const void*
                                    double radius_factor, int32_t* cand_idx, float* cand_d2, int32_t* cand_cnt, float* cand_thr,
                                    uint64_t* tiles_done, const int32_t* block_order, int n_slices, int partial_test,
                                    meld_stream_t stream);
+/* meld_knn16_topk_listed_partial with one slice that leaves the rows RAW: two half-rows [0, cap / 2) and [cap / 2, cap) of n0 and n1
+ * unsorted entries, values v = d2 - |q|^2 in scaled units, cand_cnt[q] = n0 | n1 << 16.  meld_knn_refine_sort_emit takes them as they
+ * are; meld_knn16_finish_rows turns them, in place, into what every other search entry point returns: the ksel smallest sorted by
+ * (d2, index), d2 = (v + Qn[row]) * scale_info[1] in input units, cand_cnt[row] = min(n0 + n1, ksel). */
+int meld_knn16_topk_listed_raw(const void* Q16, const float* Qn, const void* Rt16, const float* scale_info, int64_t n_ref, int d,
+                               int64_t q_count, int ksel, const uint32_t* step_list, const int32_t* step_cnt, int64_t list_stride,
+                               const float* norm2_max, int64_t q_begin, const float* thr_init, int knn, double radius_factor,
+                               int32_t* cand_idx, float* cand_d2, int32_t* cand_cnt, float* cand_thr, uint64_t* tiles_done,
+                               const int32_t* block_order, int partial_test, meld_stream_t stream);
+int meld_knn16_finish_rows(float* cand_d2, int32_t* cand_idx, int32_t* cand_cnt, const float* Qn, const float* scale_info, int64_t n_rows,
+                           int ksel, meld_stream_t stream);
 /* The partial test as a pass of its own over the step lists (round 6; the default route in the principal frame): every listed
  * (wave, tile) pair is tested on K block 0 alone against the row's START threshold (thr_init, scaled units: the seeds the lists
  * were built for) and loses its bit when no partial distance is within reach; step_list is rewritten in place, emptied entries
@@ -325,6 +336,31 @@ int meld_knn_refine(const double* X, int64_t N, int d, int64_t q_begin, int64_t 
                     const double* bw_fixed /* [N] graphtools' bandwidth= (a given bandwidth per cell, knn then only sizes the search), or NULL */,
                     int max_rank /* graphtools' knn_max + 1 (self counted): a row keeps its max_rank nearest cells at most; 0 = no limit */,
                     meld_stream_t stream);
+
+/* meld_knn_refine for ALL rows of a single-GPU build (q_begin = 0, q_count = N, no row list; even d <= 256), with the emit fused in:
+ * the kept entries of every complete row go straight into the row buckets of the symmetrisation (what meld_coo_emit_scatter would
+ * do with cand_val, which is not written) -- the row's own (idx, v / 2) pairs behind ONE atomic claim of cursor[row], every
+ * transposed copy behind one of cursor[idx].  cursor[N] is zeroed here; on return it counts what was sent to every bucket (a
+ * count above meld_csr_bucket_slots() = overflow: nothing was written beyond the bucket and the caller must rebuild the rows
+ * another way).  A row's own entries sit anywhere in its bucket: meld_csr_rows_sort_merge does not depend on the order.  bw,
+ * keep_cnt, flag_rows, n_flag as meld_knn_refine writes them.  Flagged rows emit nothing here: see meld_coo_emit_scatter_listed.
+ * X must be 16-byte aligned (MELD_ERR_INVALID otherwise): four lanes read 64 contiguous bytes of a row as pairs of doubles.
+ * The same holds for meld_knn_refine, meld_knn_radius_exact and meld_knn_pair_distances whenever d is even and <= 256. */
+int meld_knn_refine_emit(const double* X, int64_t N, int d, const int32_t* cand_idx, const float* cand_d2, const int32_t* cand_cnt,
+                         const float* cand_thr, int ksel, int cap, int knn, double decay, double thresh, const float* norm2_max,
+                         double err_coef, const float* norm2, double err_coef_lin, double* bw, int32_t* keep_cnt,
+                         int32_t* flag_rows, int32_t* n_flag, double bw_scale, const double* bw_fixed, int max_rank,
+                         int32_t* cursor, int32_t* tcol, double* tval, meld_stream_t stream);
+/* meld_knn_refine_emit on the RAW rows meld_knn16_topk_listed_raw leaves (cap = meld_knn16_row_capacity(ksel); Qn, scale_info: the
+ * search's operands): every row is ranked in registers exactly as meld_knn16_finish_rows ranks it -- the row is judged by the same
+ * fp32 values, (v + Qn[row]) * scale_info[1] -- and only the rows that end in flag_rows are written back finished (sorted entries in
+ * input units, cand_cnt[row] = min(n0 + n1, ksel)): meld_knn16_research_thresholds, the second-stage meld_knn_refine and the sweep
+ * read those.  The rows of complete rows stay raw.  Everything else as meld_knn_refine_emit. */
+int meld_knn_refine_sort_emit(const double* X, int64_t N, int d, int32_t* cand_idx, float* cand_d2, int32_t* cand_cnt, const float* Qn,
+                              const float* scale_info, const float* cand_thr, int ksel, int cap, int knn, double decay, double thresh,
+                              const float* norm2_max, double err_coef, const float* norm2, double err_coef_lin, double* bw,
+                              int32_t* keep_cnt, int32_t* flag_rows, int32_t* n_flag, double bw_scale, const double* bw_fixed, int max_rank,
+                              int32_t* cursor, int32_t* tcol, double* tval, meld_stream_t stream);
 
 /* Exact fp64 radius search for the flagged rows (the analogue of graphtools' re-search /
  * radius_neighbors fallback), rows x reference chunks over the whole device.  mode 0: fb_cnt[f] = number
@@ -467,6 +503,14 @@ int meld_coo_emit_scatter(int64_t q_count, const int32_t* cand_idx, const double
                           const int32_t* keep_cnt, const int32_t* flag_rows, int32_t n_flag, const int64_t* fb_off,
                           const int32_t* fb_col, const double* fb_val, int64_t fb_total, int32_t* cursor, int32_t* tcol,
                           double* tval, meld_stream_t stream);
+/* Behind meld_knn_refine_emit: the rows it did not emit, into the same buckets (cursor[] as it stands; every own entry behind an
+ * atomic claim, guarded by the bucket size like the transposed copies).  rows[n_rows]: the local rows of a second-stage
+ * meld_knn_refine (cand_val [.][ksel] / cand_idx [.][cap] at the local row; rows with keep_cnt 0 -- still flagged, or empty --
+ * are skipped); flag_rows / fb_*: the entries of the exact sweep, as for meld_coo_emit_scatter.  Either part may be empty. */
+int meld_coo_emit_scatter_listed(const int32_t* rows, int32_t n_rows, const int32_t* cand_idx, const double* cand_val, int ksel,
+                                 int cap, const int32_t* keep_cnt, const int32_t* flag_rows, int32_t n_flag, const int64_t* fb_off,
+                                 const int32_t* fb_col, const double* fb_val, int64_t fb_total, int32_t* cursor, int32_t* tcol,
+                                 double* tval, meld_stream_t stream);
 int meld_csr_bucket_slots(void);
 int meld_coo_scatter_rows(const uint64_t* keys, const double* vals, int64_t n, int64_t row_begin, int64_t n_rows,
                           int32_t* cursor, int32_t* tcol, double* tval, meld_stream_t stream);

@@ -36,6 +36,16 @@ SIGNATURES = {
         [_ptr, _i64, _i32, _i64, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _f64, _f64, _ptr, _f64, _ptr, _f64, _ptr, _ptr, _ptr,
          _ptr, _ptr, _ptr, _i32, _ptr, _f64, _ptr, _i32, _ptr],
     ),
+    "meld_knn_refine_emit": (
+        _i32,
+        [_ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _f64, _f64, _ptr, _f64, _ptr, _f64, _ptr, _ptr, _ptr, _ptr, _f64, _ptr,
+         _i32, _ptr, _ptr, _ptr, _ptr],
+    ),
+    "meld_knn_refine_sort_emit": (
+        _i32,
+        [_ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _i32, _f64, _f64, _ptr, _f64, _ptr, _f64, _ptr, _ptr, _ptr, _ptr, _f64,
+         _ptr, _i32, _ptr, _ptr, _ptr, _ptr],
+    ),
     "meld_knn_error_coef": (_f64, [_i32]),
     "meld_knn16_kblocks": (_i32, [_i32]),
     "meld_knn16_tile_refs": (_i32, []),
@@ -69,6 +79,8 @@ SIGNATURES = {
     "meld_knn16_step_lists_direct_lead": (_i32, [_ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _i32, _ptr]),
     "meld_knn16_topk_listed": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _i32, _i64, _i32, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i32, _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr]),
     "meld_knn16_topk_listed_partial": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _i32, _i64, _i32, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i32, _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i32, _ptr]),
+    "meld_knn16_topk_listed_raw": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _i32, _i64, _i32, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i32, _f64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _i32, _ptr]),
+    "meld_knn16_finish_rows": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i32, _ptr]),
     "meld_knn16_partial_filter": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _i32, _i64, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
     "meld_knn16_seed_thresholds_mfma": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _i32, _i64, _i64, _i32, _f64, _i32, _i32, _ptr, _ptr]),
     "meld_knn16_max_slices": (_i32, [_i32]),
@@ -107,6 +119,7 @@ SIGNATURES = {
     "meld_csr_bucket_slots": (_i32, []),
     "meld_coo_scatter_rows": (_i32, [_ptr, _ptr, _i64, _i64, _i64, _ptr, _ptr, _ptr, _ptr]),
     "meld_coo_emit_scatter": (_i32, [_i64, _ptr, _ptr, _i32, _i32, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "meld_coo_emit_scatter_listed": (_i32, [_ptr, _i32, _ptr, _ptr, _i32, _i32, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
     "meld_coo_partition_remote": (_i32, [_ptr, _ptr, _i64, _i64, _i32, _i32, _i64, _ptr, _ptr, _ptr]),
     "meld_csr_rows_sort_merge": (_i32, [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _i32, _f64, _ptr]),
     "meld_csr_compact_rows": (_i32, [_ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr]),

@@ -21,7 +21,9 @@ MELD_SHARDED_C_LOOPS    1           row-sharded recurrences enqueued from C on t
 
 Development switches are read where they are used, through ``opt``; among them ``MELD_METRIC_PRUNE`` (default 1; 0: the L1 /
 L-infinity candidate search of ``meld_amd.metric_knn`` visits every tile instead of skipping those its box bound rules out --
-the same graph bit for bit, for A-B measurements and tests).
+the same graph bit for bit, for A-B measurements and tests) and ``MELD_ROWS_FUSED`` (default b; 0: the finish, refinement and emit
+kernels behind the search run one by one, a: the refinement emits but takes finished rows, b: it also ranks the raw rows --
+``knn_plan.plan_fused_rows``; the same graph bit for bit).
 """
 import os
 

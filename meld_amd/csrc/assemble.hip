@@ -309,7 +309,7 @@ __device__ __forceinline__ void coo_row_run(int64_t r, int lane, bool* leader, i
 }
 
 // row r's bucket = slots [r * CSR_BUCKET, (r + 1) * CSR_BUCKET) of tcol / tval; cursor[r] counts what was sent to it
-constexpr int CSR_BUCKET = 256;
+// (CSR_BUCKET = 256: common.hpp)
 
 __global__ __launch_bounds__(256) void coo_scatter_rows_kernel(const unsigned long long* __restrict__ keys,
                                                                const double* __restrict__ vals, int64_t n, int64_t row_begin,
@@ -389,15 +389,24 @@ __global__ __launch_bounds__(256) void coo_partition_remote_kernel(const unsigne
 // its own entries into the first keep_cnt[q] slots of bucket q (no atomic: cursor[] starts at keep_cnt[]), the transposed
 // copy of each into the bucket of its column's row behind an atomic slot -- instead of being written as 2 M (key, value)
 // pairs (512 MB at 1M cells) that the scatter kernel reads back.  cursor ends as meld_coo_scatter_rows leaves it.
+// CLAIM (behind meld_knn_refine_emit, whose cursor starts at zero): the wave takes row rows[i] of a list and claims the row's own
+// slots by one atomicAdd(cursor + row, keep_cnt[row]).
+template <bool CLAIM>
 __global__ __launch_bounds__(256) void coo_emit_scatter_rows_kernel(int64_t q_count, const int* __restrict__ cand_idx,
                                                                     const double* __restrict__ cand_val, int ksel, int cap,
                                                                     const int* __restrict__ keep_cnt, int* __restrict__ cursor,
-                                                                    int* __restrict__ tcol, double* __restrict__ tval) {
+                                                                    int* __restrict__ tcol, double* __restrict__ tval,
+                                                                    const int* __restrict__ rows) {
   const int lane = threadIdx.x & 63;
-  const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (q >= q_count) return;
+  const int64_t qi = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (qi >= q_count) return;
+  const int64_t q = CLAIM ? (int64_t)rows[qi] : qi;
   if (keep_cnt[q] == 0) return;  // flagged (its entries come from the exact sweep) or empty row
   int written = 0;
+  if constexpr (CLAIM) {
+    if (lane == 0) written = atomicAdd(cursor + q, keep_cnt[q]);
+    written = __builtin_amdgcn_readfirstlane(written);
+  }
   for (int c0 = 0; c0 < ksel; c0 += 64) {
     const int c = c0 + lane;
     double v = 0.0;
@@ -411,8 +420,10 @@ __global__ __launch_bounds__(256) void coo_emit_scatter_rows_kernel(int64_t q_co
     if (keep) {
       const int pos = written + __popcll(b & ((1ull << lane) - 1ull));
       const double hv = 0.5 * v;
-      tcol[q * CSR_BUCKET + pos] = j;  // (pos < keep_cnt[q] <= ksel <= CSR_BUCKET)
-      tval[q * CSR_BUCKET + pos] = hv;
+      if (!CLAIM || pos < CSR_BUCKET) {  // (without CLAIM pos < keep_cnt[q] <= ksel <= CSR_BUCKET)
+        tcol[q * CSR_BUCKET + pos] = j;
+        tval[q * CSR_BUCKET + pos] = hv;
+      }
       const int slot = atomicAdd(cursor + j, 1);
       if (slot < CSR_BUCKET) {  // (an overfull bucket shows in cursor[j]: the caller takes the sort-based path)
         tcol[(int64_t)j * CSR_BUCKET + slot] = (int)q;
@@ -423,7 +434,8 @@ __global__ __launch_bounds__(256) void coo_emit_scatter_rows_kernel(int64_t q_co
   }
 }
 // ... and the entries of the rows the exact sweep recomputed (thread per entry): fb_off[k] .. fb_off[k + 1] belong to row
-// flag_rows[k], whose cursor started at their count
+// flag_rows[k], whose cursor started at their count (CLAIM: at whatever it holds -- every entry claims its own slot)
+template <bool CLAIM>
 __global__ __launch_bounds__(256) void coo_emit_scatter_fallback_kernel(const int* __restrict__ flag_rows, int n_flag,
                                                                         const int64_t* __restrict__ fb_off,
                                                                         const int* __restrict__ fb_col,
@@ -438,7 +450,7 @@ __global__ __launch_bounds__(256) void coo_emit_scatter_fallback_kernel(const in
     if (fb_off[mid] <= e) lo = mid; else hi = mid - 1;
   }
   const int64_t q = flag_rows[lo];
-  const int64_t pos = e - fb_off[lo];
+  const int64_t pos = CLAIM ? (int64_t)atomicAdd(cursor + q, 1) : e - fb_off[lo];
   const int j = fb_col[e];
   const double hv = 0.5 * fb_val[e];
   if (pos < CSR_BUCKET) {
@@ -769,14 +781,39 @@ extern "C" int meld_coo_emit_scatter(int64_t q_count, const int32_t* cand_idx, c
   MELD_CHECK_ARG(cand_idx && cand_val && keep_cnt && cursor && tcol && tval && q_count > 0, "meld_coo_emit_scatter: bad arguments");
   MELD_CHECK_ARG(cap >= ksel && ksel <= CSR_BUCKET, "meld_coo_emit_scatter: ksel=%d must fit a row bucket (%d) and the row stride cap=%d",
                  ksel, CSR_BUCKET, cap);
-  hipLaunchKernelGGL(coo_emit_scatter_rows_kernel, dim3((unsigned)ceil_div(q_count, 4)), dim3(256), 0, S(stream), q_count, cand_idx,
-                     cand_val, ksel, cap, keep_cnt, cursor, tcol, tval);
+  hipLaunchKernelGGL(coo_emit_scatter_rows_kernel<false>, dim3((unsigned)ceil_div(q_count, 4)), dim3(256), 0, S(stream), q_count, cand_idx,
+                     cand_val, ksel, cap, keep_cnt, cursor, tcol, tval, (const int*)nullptr);
   MELD_LAUNCH_CHECK("coo_emit_scatter_rows_kernel");
   if (n_flag > 0 && fb_total > 0) {
     MELD_CHECK_ARG(flag_rows && fb_off && fb_col && fb_val, "meld_coo_emit_scatter: missing fallback arrays");
-    hipLaunchKernelGGL(coo_emit_scatter_fallback_kernel, dim3((unsigned)ceil_div(fb_total, 256)), dim3(256), 0, S(stream), flag_rows,
+    hipLaunchKernelGGL(coo_emit_scatter_fallback_kernel<false>, dim3((unsigned)ceil_div(fb_total, 256)), dim3(256), 0, S(stream), flag_rows,
                        n_flag, fb_off, fb_col, fb_val, fb_total, cursor, tcol, tval);
     MELD_LAUNCH_CHECK("coo_emit_scatter_fallback_kernel");
+  }
+  return MELD_OK;
+}
+
+// What meld_knn_refine_emit left out, into the buckets it filled (cursor[] as it stands, every own entry behind an atomic claim):
+// the rows rows[0 .. n_rows) of a second-stage meld_knn_refine (cand_val / cand_idx at the local row; those still flagged have
+// keep_cnt 0 and are skipped), and the entries of the exact sweep (fb_off[k] .. fb_off[k + 1] belong to row flag_rows[k]).
+extern "C" int meld_coo_emit_scatter_listed(const int32_t* rows, int32_t n_rows, const int32_t* cand_idx, const double* cand_val, int ksel,
+                                            int cap, const int32_t* keep_cnt, const int32_t* flag_rows, int32_t n_flag,
+                                            const int64_t* fb_off, const int32_t* fb_col, const double* fb_val, int64_t fb_total,
+                                            int32_t* cursor, int32_t* tcol, double* tval, meld_stream_t stream) {
+  MELD_CHECK_ARG(cursor && tcol && tval && n_rows >= 0 && n_flag >= 0 && fb_total >= 0, "meld_coo_emit_scatter_listed: bad arguments");
+  if (n_rows > 0) {
+    MELD_CHECK_ARG(rows && cand_idx && cand_val && keep_cnt, "meld_coo_emit_scatter_listed: missing candidate arrays");
+    MELD_CHECK_ARG(cap >= ksel && ksel >= 1 && ksel <= CSR_BUCKET, "meld_coo_emit_scatter_listed: ksel=%d must fit a row bucket (%d) and the row stride cap=%d",
+                   ksel, CSR_BUCKET, cap);
+    hipLaunchKernelGGL(coo_emit_scatter_rows_kernel<true>, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, S(stream), (int64_t)n_rows,
+                       cand_idx, cand_val, ksel, cap, keep_cnt, cursor, tcol, tval, rows);
+    MELD_LAUNCH_CHECK("coo_emit_scatter_rows_kernel<listed>");
+  }
+  if (n_flag > 0 && fb_total > 0) {
+    MELD_CHECK_ARG(flag_rows && fb_off && fb_col && fb_val, "meld_coo_emit_scatter_listed: missing fallback arrays");
+    hipLaunchKernelGGL(coo_emit_scatter_fallback_kernel<true>, dim3((unsigned)ceil_div(fb_total, 256)), dim3(256), 0, S(stream), flag_rows,
+                       n_flag, fb_off, fb_col, fb_val, fb_total, cursor, tcol, tval);
+    MELD_LAUNCH_CHECK("coo_emit_scatter_fallback_kernel<claim>");
   }
   return MELD_OK;
 }

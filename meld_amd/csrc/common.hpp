@@ -55,6 +55,9 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// slots of a row bucket of the symmetrisation (assemble.hip; refine.hip's emitting kernel writes into the buckets too)
+constexpr int CSR_BUCKET = 256;
+
 // Development switches of the library (A-B measurements, ablations, counters): read only under MELD_DEV=1, so that a stray
 // variable in a production environment cannot change which kernels run (the same rule as meld_amd/_options.py on the host side)
 static inline const char* meld_dev_getenv(const char* name) {

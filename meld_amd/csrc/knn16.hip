@@ -32,6 +32,7 @@
 // Radius cut: once a row holds knn + 1 entries its threshold drops to the kernel radius that entry
 // implies (knn16_squeeze_row), and the final threshold is published for refine's completeness test.
 #include "common.hpp"
+#include "k16_rows.hpp"
 
 #include <hip/hip_fp16.h>
 
@@ -44,7 +45,7 @@ constexpr int K16_BQ = 256;        // queries per workgroup
 constexpr int K16_THREADS = 256;   // four waves of 64 queries each; 2-3 workgroups resident per CU
 constexpr int K16_NWAVE = K16_THREADS / 64;
 constexpr int K16_SLACK = 128;     // CAP = ksel + slack
-constexpr int K16_CAPMAX = 256;
+constexpr int K16_CAPMAX = K16_ROW_CAPMAX;  // (k16_rows.hpp)
 // Centroids per workgroup of the pruning-table kernel (64 per wave).  Every workgroup streams all cells of its query
 // slice past its centroids, so the tile traffic is N x d x 2 B x (tiles / centroids per workgroup): 7.9 GB at 1M cells
 // with 256 centroids (the kernel was bound by it, not by its MFMAs or the per-distance VALU work), 2 GB with 1024.
@@ -94,10 +95,6 @@ __device__ __forceinline__ float min16(const f32x16& v) {
   return __builtin_fminf(min3f(a, b, v[15]), min3f(c, d, e));
 }
 
-__device__ __forceinline__ unsigned ordered_bits(float f) {
-  const unsigned b = __float_as_uint(f);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
 
 __device__ __forceinline__ float ld_sc1_f(const float* p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -132,9 +129,6 @@ __device__ __forceinline__ int knn16_split_pos(int pos, int m0, int half) { retu
 // Keep (unsorted) the entries of a candidate row whose d2 is <= the ksel-th smallest d2, spread evenly
 // over the two half-rows.  Returns the new lengths through *n0_out / *n1_out and the threshold as
 // return value.  Wave-uniform arguments.
-__device__ __forceinline__ float from_ordered_bits(unsigned k) {
-  return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
 
 // Radius cut (knn1 > 0): with A = the knn1-th smallest d2 of the row (knn1 = knn + 1, self included) and E
 // the search-error allowance of the row, the exact bandwidth^2 is <= A + E, so every reference inside the
@@ -1287,38 +1281,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 // lane and the others are one __shfl_xor), keeps the ksel smallest, converts them to input units
 // ((v + |q|^2) / s^2) and writes the row's length.  cnt: in = half-row lengths n0 | n1 << 16, out = min(n, ksel).
 // 1M rows of <= 128 entries: 0.8 ms (the in-kernel ranking it replaces: 4.8 ms).
-template <int SL>
-__device__ __forceinline__ void k16_bitonic_sort(unsigned long long (&key)[SL], int lane) {
-  constexpr int NE = 64 * SL;
-#pragma unroll
-  for (int k = 2; k <= NE; k <<= 1) {
-#pragma unroll
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      if (j >= 64) {
-        const int je = j >> 6;
-#pragma unroll
-        for (int e = 0; e < SL; ++e) {
-          if ((e & je) == 0) {
-            const int i = 64 * e + lane;
-            const bool asc = (i & k) == 0;
-            const unsigned long long a = key[e], b = key[e | je];
-            const bool sw = asc ? (b < a) : (a < b);
-            key[e] = sw ? b : a;
-            key[e | je] = sw ? a : b;
-          }
-        }
-      } else {
-#pragma unroll
-        for (int e = 0; e < SL; ++e) {
-          const int i = 64 * e + lane;
-          const unsigned long long o = __shfl_xor(key[e], j, 64);
-          const bool keep_min = ((i & j) == 0) == ((i & k) == 0);
-          key[e] = keep_min ? (o < key[e] ? o : key[e]) : (o < key[e] ? key[e] : o);
-        }
-      }
-    }
-  }
-}
+// (k16_bitonic_sort: k16_rows.hpp)
 // (the network is as small as the row allows: most rows hold fewer than 128 entries, many fewer than 64)
 template <int SL>
 __device__ __forceinline__ void k16_finish_row(float* __restrict__ drow, int* __restrict__ irow, int n0, int half, int n_all, int n,
@@ -2965,8 +2928,10 @@ static int k16_topk_impl(const void* Q16, const float* Qn, const void* Rt16, con
                          const float* norm2_max, int64_t q_begin, const float* thr_init, int knn,
                          double radius_factor, int32_t* cand_idx, float* cand_d2, int32_t* cand_cnt,
                          float* cand_thr, uint64_t* tiles_done, const int32_t* block_order, const uint32_t* step_list,
-                         const int32_t* step_cnt, int64_t list_stride, meld_stream_t stream, int partial_test = 0, int two_counters = 0) {
+                         const int32_t* step_cnt, int64_t list_stride, meld_stream_t stream, int partial_test = 0, int two_counters = 0,
+                         bool finish = true) {
   MELD_CHECK_ARG(nprod == 1 || nprod == 3, "meld_knn16_topk: nprod must be 1 or 3");
+  MELD_CHECK_ARG(finish || n_slices == 1, "meld_knn16_topk_listed_raw: raw rows go with one slice (the merge of slices takes finished rows)");
   MELD_CHECK_ARG(step_list == nullptr || (step_cnt != nullptr && nprod == 1 && lb2 == nullptr && thr_init != nullptr),
                  "meld_knn16_topk_listed: step lists go with the hi-only pass, start thresholds and no table");
   // (reference slices combine with pruning, the radius cut and a dispatch order: a slice's table row is the wave's row, its
@@ -3067,10 +3032,12 @@ static int k16_topk_impl(const void* Q16, const float* Qn, const void* Rt16, con
   }
 #undef K16_CASE
   MELD_LAUNCH_CHECK("knn16_topk_kernel");
-  const int64_t n_rows = (int64_t)grid.x * K16_BQ * grid.y;
-  hipLaunchKernelGGL(knn16_finish_rows_kernel, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, S(stream), cand_d2, cand_idx, cand_cnt, Qn,
-                     scale_info, n_rows, (int64_t)grid.y * K16_BQ, cap, ksel);
-  MELD_LAUNCH_CHECK("knn16_finish_rows_kernel");
+  if (finish) {
+    const int64_t n_rows = (int64_t)grid.x * K16_BQ * grid.y;
+    hipLaunchKernelGGL(knn16_finish_rows_kernel, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, S(stream), cand_d2, cand_idx, cand_cnt, Qn,
+                       scale_info, n_rows, (int64_t)grid.y * K16_BQ, cap, ksel);
+    MELD_LAUNCH_CHECK("knn16_finish_rows_kernel");
+  }
   if (stats) {
     unsigned long long st[13] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     MELD_HIP_CALL(hipStreamSynchronize(S(stream)));
@@ -3130,6 +3097,33 @@ extern "C" int meld_knn16_topk_listed_partial(const void* Q16, const float* Qn, 
   return k16_topk_impl(Q16, Qn, Rt16, scale_info, n_ref, d, q_count, ksel, 1, n_slices, nullptr, norm2_max, q_begin, thr_init, knn,
                        radius_factor, cand_idx, cand_d2, cand_cnt, cand_thr, tiles_done, block_order, step_list, step_cnt, list_stride,
                        stream, partial_test, 1);
+}
+
+// meld_knn16_topk_listed_partial with one slice, and the rows left RAW: two half-rows of accumulator values v = d2 - |q|^2 in
+// scaled units, unsorted, cand_cnt[q] = n0 | n1 << 16 -- what meld_knn_refine_sort_emit ranks in registers.  meld_knn16_finish_rows
+// makes of them the rows every other entry point returns.
+extern "C" int meld_knn16_topk_listed_raw(const void* Q16, const float* Qn, const void* Rt16, const float* scale_info, int64_t n_ref,
+                                          int d, int64_t q_count, int ksel, const uint32_t* step_list, const int32_t* step_cnt,
+                                          int64_t list_stride, const float* norm2_max, int64_t q_begin, const float* thr_init, int knn,
+                                          double radius_factor, int32_t* cand_idx, float* cand_d2, int32_t* cand_cnt, float* cand_thr,
+                                          uint64_t* tiles_done, const int32_t* block_order, int partial_test, meld_stream_t stream) {
+  MELD_CHECK_ARG(step_list && step_cnt && list_stride > 0, "meld_knn16_topk_listed_raw: null step lists");
+  return k16_topk_impl(Q16, Qn, Rt16, scale_info, n_ref, d, q_count, ksel, 1, 1, nullptr, norm2_max, q_begin, thr_init, knn,
+                       radius_factor, cand_idx, cand_d2, cand_cnt, cand_thr, tiles_done, block_order, step_list, step_cnt, list_stride,
+                       stream, partial_test, 1, false);
+}
+
+// Raw candidate rows [n_rows][cap] (cap = meld_knn16_row_capacity(ksel)) -> finished ones, in place: the ksel smallest sorted by
+// (d2, index), d2 = (v + Qn[row]) * scale_info[1] in input units, cand_cnt[row] = min(n0 + n1, ksel).
+extern "C" int meld_knn16_finish_rows(float* cand_d2, int32_t* cand_idx, int32_t* cand_cnt, const float* Qn, const float* scale_info,
+                                      int64_t n_rows, int ksel, meld_stream_t stream) {
+  MELD_CHECK_ARG(cand_d2 && cand_idx && cand_cnt && Qn && scale_info && n_rows > 0, "meld_knn16_finish_rows: bad arguments");
+  const int cap = meld_knn16_row_capacity(ksel);
+  if (cap < 0) return cap;
+  hipLaunchKernelGGL(knn16_finish_rows_kernel, dim3((unsigned)ceil_div(n_rows, 4)), dim3(256), 0, S(stream), cand_d2, cand_idx, cand_cnt, Qn,
+                     scale_info, n_rows, n_rows, cap, ksel);
+  MELD_LAUNCH_CHECK("knn16_finish_rows_kernel");
+  return MELD_OK;
 }
 
 // The partial-distance test as a pass over the step lists (knn16_partial_filter_kernel): lists built for operands in the SPLIT

@@ -17,9 +17,11 @@
 // and the row of K computed from the candidates are exact.  Rows that fail the test are
 // flagged and recomputed by the exact fp64 sweep below -- graphtools' re-search fallback.
 #include "common.hpp"
+#include "k16_rows.hpp"
 
 #include <algorithm>
 #include <cfloat>
+#include <cstdint>
 
 namespace meld {
 
@@ -83,7 +85,34 @@ __device__ __forceinline__ double decay_kernel(double dist, double bw, double de
 // at the rate of the vector L1, not of anything behind it: 1.5e9 tag accesses (TCP_TOTAL_CACHE_ACCESSES) in 7.4 M cycles on 256
 // CUs, TCP busy (TCP_GATE_EN1) 96 % of the time, L2 hit rate 85 %, 2.5-5 GB from the fabric for 18.7 GB gathered
 // (profiles/r06_refine_pmc.txt).  The query row sits in LDS; the four lanes' partial sums meet by two DPP exchanges.
-template <bool COOP>
+// A raw candidate row of the split-fp16 search (two half-rows of n0 and n_all - n0 unsorted entries) ranked in registers exactly as
+// knn16_finish_rows_kernel ranks it: 64-bit keys (ordered bits of v + 0 : index), the smallest network that holds the row; out[e] =
+// the key of rank 64 e + lane (e < 2: at most 128 entries are kept), ~0 behind the row's end.
+template <int SL>
+__device__ __forceinline__ void rf_rank_raw_row(const float* drow, const int* irow, int n0, int half, int n_all, int lane,
+                                                unsigned long long (&out)[2]) {
+  unsigned long long key[SL];
+#pragma unroll
+  for (int e = 0; e < SL; ++e) {
+    const int i = lane + 64 * e;
+    const int p = i < n0 ? i : half + (i - n0);
+    key[e] = ~0ull;
+    if (i < n_all) key[e] = ((unsigned long long)ordered_bits(drow[p] + 0.0f) << 32) | (unsigned)irow[p];  // (+0: -0 and +0 tie)
+  }
+  k16_bitonic_sort<SL>(key, lane);
+  out[0] = key[0];
+  out[1] = SL > 1 ? key[SL > 1 ? 1 : 0] : ~0ull;
+}
+
+// EMIT (with COOP, every row local: q_begin = 0, no row list): a complete row sends its kept entries straight to the row buckets of
+// the symmetrisation (csrc/assemble.hip) instead of storing their values for coo_emit_scatter_rows_kernel to load back -- ONE
+// atomicAdd(cursor + row, kept) claims the row's own slots, one atomicAdd(cursor + j, 1) each transposed copy's; cursor starts at
+// zero.  A row's own entries then sit anywhere in its bucket, which csr_rows_sort_merge_kernel does not depend on.  cand_val is not
+// touched; bw, keep_cnt, flag_rows and n_flag are written as without EMIT.
+// RAW (with EMIT): the rows come as the search leaves them (raw_idx / raw_d2 / raw_cnt = n0 | n1 << 16, see rf_rank_raw_row) and are
+// ranked here; the values the row is judged by are knn16_finish_rows_kernel's, (v + Qn[row]) * scale_info[1], bit for bit.  Only a
+// row that is flagged is written back finished (sorted entries, raw_cnt = min(n, ksel)): the re-search and the sweep read those.
+template <bool COOP, bool EMIT = false, bool RAW = false>
 __global__ __launch_bounds__(256) void refine_kernel(
     const double* __restrict__ X, int d, int64_t q_begin, int64_t q_count, const int* __restrict__ cand_idx,
     const float* __restrict__ cand_d2, const int* __restrict__ cand_cnt, const float* __restrict__ cand_thr, int ksel,
@@ -91,7 +120,10 @@ __global__ __launch_bounds__(256) void refine_kernel(
     const float* __restrict__ norm2, double err_coef_lin, double bw_scale, const double* __restrict__ bw_fixed, int max_rank,
     double* __restrict__ bw_out, double* __restrict__ cand_val, int* __restrict__ keep_cnt,
     int* __restrict__ flag_rows, int* __restrict__ n_flag, const int* __restrict__ rows, int out_cap,
-    int* __restrict__ cand_idx_out) {
+    int* __restrict__ cand_idx_out, int* __restrict__ cursor = nullptr, int* __restrict__ tcol = nullptr,
+    double* __restrict__ tval = nullptr, int* raw_idx = nullptr, float* raw_d2 = nullptr, int* raw_cnt = nullptr,
+    const float* __restrict__ Qn = nullptr, const float* __restrict__ scale_info = nullptr) {
+  static_assert((COOP || !EMIT) && (EMIT || !RAW), "the emitting forms exist for the four-chain kernel only");
   const int lane = threadIdx.x & 63;
   const int64_t q = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (q >= q_count) return;
@@ -105,7 +137,28 @@ __global__ __launch_bounds__(256) void refine_kernel(
   // chain count -> entry knn -> entries cost three round trips to L2 per row, a third of the kernel's time without its gather)
   int idx_raw[2] = {0, 0};
   float d2_raw[2] = {0.0f, 0.0f}, d2_knn = 0.0f;
-  if constexpr (COOP) {
+  int n_raw = 0;
+  if constexpr (RAW) {
+    const int packed = raw_cnt[q];
+    const int n0 = packed & 0xffff, n_all = n0 + ((packed >> 16) & 0xffff);
+    const float add = Qn[q], out_scale = scale_info[1];
+    unsigned long long key[2];
+    // (every load of the row happens before its first store: all lanes of the wave pass the sort's shuffles in between)
+    if (n_all <= 64)
+      rf_rank_raw_row<1>(raw_d2 + ro, raw_idx + ro, n0, cap >> 1, n_all, lane, key);
+    else if (n_all <= 128)
+      rf_rank_raw_row<2>(raw_d2 + ro, raw_idx + ro, n0, cap >> 1, n_all, lane, key);
+    else
+      rf_rank_raw_row<K16_ROW_SLOTS>(raw_d2 + ro, raw_idx + ro, n0, cap >> 1, n_all, lane, key);
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      idx_raw[e] = (int)(unsigned)key[e];
+      d2_raw[e] = (from_ordered_bits((unsigned)(key[e] >> 32)) + add) * out_scale;
+    }
+    const float k_lo = __shfl(d2_raw[0], knn & 63, 64), k_hi = __shfl(d2_raw[1], knn & 63, 64);
+    d2_knn = knn < 64 ? k_lo : k_hi;  // (used where n > knn only)
+    n_raw = min(n_all, ksel);
+  } else if constexpr (COOP) {
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       const int cc = min(lane + 64 * e, cap - 1);
@@ -114,7 +167,9 @@ __global__ __launch_bounds__(256) void refine_kernel(
     }
     d2_knn = cand_d2[ro + min(knn, cap - 1)];
   }
-  const int n = min(cand_cnt[q], ksel);
+  int n_list;
+  if constexpr (RAW) n_list = n_raw; else n_list = min(cand_cnt[q], ksel);
+  const int n = n_list;
 
   // search-error allowance: constant part + the part that scales with this row's own norm
   // (|q.r - q~.r~| <= c_lin |x_q| max|x_r|, the per-row form of the Cauchy-Schwarz bound)
@@ -296,7 +351,12 @@ __global__ __launch_bounds__(256) void refine_kernel(
   // tau: every reference that is not in the list has approximate d2 >= tau -- the last entry of a full
   // list, or the threshold the search published for a row it cut at the kernel radius (cand_thr)
   double tau = INFINITY;
-  if (cand_cnt[q] >= ksel) tau = (double)cand_d2[ro + ksel - 1];
+  if constexpr (RAW) {
+    const float t_lo = __shfl(d2_raw[0], (ksel - 1) & 63, 64), t_hi = __shfl(d2_raw[1], (ksel - 1) & 63, 64);
+    if (n >= ksel) tau = (double)(ksel <= 64 ? t_lo : t_hi);
+  } else {
+    if (cand_cnt[q] >= ksel) tau = (double)cand_d2[ro + ksel - 1];
+  }
   if (cand_thr != nullptr) tau = fmin(tau, (double)cand_thr[q]);
   bool complete = (reach * reach + E <= tau);
   // graphtools' knn_max (max_rank = knn_max + 1, self counted; 0 = none): a row keeps its max_rank nearest cells at most.  The
@@ -314,6 +374,8 @@ __global__ __launch_bounds__(256) void refine_kernel(
   if (bw_fixed == nullptr && n <= knn) complete = false;  // cannot even define the bandwidth from this list
 
   int kept = 0;
+  double vk[2];
+  unsigned long long kb[2];
 #pragma unroll
   for (int e = 0; e < 2; ++e) {
     const int c = lane + 64 * e;
@@ -323,11 +385,52 @@ __global__ __launch_bounds__(256) void refine_kernel(
       if (v < thresh || (int64_t)idx[e] == gi) v = 0.0;  // diagonal handled analytically (K_ii = 1)
       if (max_rank > 0 && rk[e] >= max_rank) v = 0.0;    // beyond the knn_max nearest
     }
-    if (c < ksel) {
-      cand_val[(size_t)orow * ksel + c] = v;
-      if (cand_idx_out) cand_idx_out[(size_t)orow * out_cap + c] = (c < n) ? idx[e] : 0;
+    if constexpr (!EMIT) {
+      if (c < ksel) {
+        cand_val[(size_t)orow * ksel + c] = v;
+        if (cand_idx_out) cand_idx_out[(size_t)orow * out_cap + c] = (c < n) ? idx[e] : 0;
+      }
     }
-    kept += __popcll(__ballot(v > 0.0));
+    vk[e] = v;
+    kb[e] = __ballot(v > 0.0);
+    kept += __popcll(kb[e]);
+  }
+  if constexpr (EMIT) {
+    if (kept > 0) {  // (uniform; v > 0 on complete rows only)
+      int base = 0;
+      if (lane == 0) base = atomicAdd(cursor + gi, kept);
+      base = __builtin_amdgcn_readfirstlane(base);
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        if (vk[e] > 0.0) {
+          const int pos = base + (e ? __popcll(kb[0]) : 0) + __popcll(kb[e] & ((1ull << lane) - 1ull));
+          const int j = idx[e];
+          const double hv = 0.5 * vk[e];
+          if (pos < CSR_BUCKET) {  // (an overfull bucket shows in cursor[]: the caller recovers)
+            tcol[gi * CSR_BUCKET + pos] = j;
+            tval[gi * CSR_BUCKET + pos] = hv;
+          }
+          const int slot = atomicAdd(cursor + j, 1);
+          if (slot < CSR_BUCKET) {
+            tcol[(int64_t)j * CSR_BUCKET + slot] = (int)gi;
+            tval[(int64_t)j * CSR_BUCKET + slot] = hv;
+          }
+        }
+      }
+    }
+  }
+  if constexpr (RAW) {
+    if (!complete) {  // (uniform) the finished row, for the re-search's thresholds, the second stage's hand-over and the sweep
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int c = lane + 64 * e;
+        if (c < n) {
+          raw_d2[ro + c] = d2_raw[e];
+          raw_idx[ro + c] = idx_raw[e];
+        }
+      }
+      if (lane == 0) raw_cnt[q] = n;
+    }
   }
   if (lane == 0) {
     bw_out[orow] = bw_raw;
@@ -539,6 +642,7 @@ extern "C" int meld_knn_refine(const double* X, int64_t N, int d, int64_t q_begi
   MELD_CHECK_ARG(err_coef >= 0 && err_coef_lin >= 0, "meld_knn_refine: error coefficients must be non-negative");
   MELD_CHECK_ARG(bw_scale > 0 && bw_scale < INFINITY, "meld_knn_refine: bandwidth_scale must be positive and finite");
   MELD_CHECK_ARG(max_rank == 0 || max_rank > knn, "meld_knn_refine: max_rank=%d must exceed knn=%d (or be 0)", max_rank, knn);
+  MELD_CHECK_ARG(!rf_four_chains(d) || ((uintptr_t)X & 15) == 0, "meld_knn_refine: X must be 16-byte aligned (even d <= %d)", RF_DMAX);
   const double radius_factor = pow(-log(thresh), 1.0 / decay);
 #define RF_LAUNCH(COOPV)                                                                                                          \
   hipLaunchKernelGGL(refine_kernel<COOPV>, dim3((unsigned)ceil_div(q_count, 4)), dim3(256), 0, S(stream), X, d, q_begin, q_count,  \
@@ -554,6 +658,68 @@ extern "C" int meld_knn_refine(const double* X, int64_t N, int d, int64_t q_begi
   return MELD_OK;
 }
 
+// meld_knn_refine for ALL rows of a single-GPU build (row q = cell q, candidates of the split-fp16 search), with the kept entries of
+// the complete rows sent straight to the row buckets: cursor[N] is zeroed here and ends counting what was sent to every bucket
+// (above meld_csr_bucket_slots(): overflow, nothing written beyond the bucket).  No cand_val: the flagged rows' entries come from
+// the second-stage refinement / the exact sweep through meld_coo_emit_scatter_listed.  Qn != NULL: the rows are raw (refine_kernel, RAW).
+static int refine_emit_impl(const char* who, const double* X, int64_t N, int d, int32_t* cand_idx, float* cand_d2, int32_t* cand_cnt,
+                            const float* Qn, const float* scale_info, const float* cand_thr, int ksel, int cap, int knn, double decay,
+                            double thresh, const float* norm2_max, double err_coef, const float* norm2, double err_coef_lin, double* bw,
+                            int32_t* keep_cnt, int32_t* flag_rows, int32_t* n_flag, double bw_scale, const double* bw_fixed, int max_rank,
+                            int32_t* cursor, int32_t* tcol, double* tval, meld_stream_t stream) {
+  MELD_CHECK_ARG(X && cand_idx && cand_d2 && cand_cnt && norm2_max && bw && keep_cnt && flag_rows && n_flag && cursor && tcol && tval,
+                 "%s: null pointer", who);
+  MELD_CHECK_ARG(N > 0 && N < (int64_t)1 << 31 && rf_four_chains(d), "%s: needs 0 < N < 2^31 and an even d <= %d (d=%d)", who, RF_DMAX, d);
+  MELD_CHECK_ARG(((uintptr_t)X & 15) == 0, "%s: X must be 16-byte aligned", who);
+  MELD_CHECK_ARG(ksel >= 1 && ksel <= 128 && ksel <= CSR_BUCKET, "%s: ksel=%d outside [1,128]", who, ksel);
+  MELD_CHECK_ARG(knn >= 0 && decay > 0 && thresh > 0 && thresh <= 1, "%s: bad kernel parameters", who);
+  MELD_CHECK_ARG(cap >= ksel, "%s: row stride cap=%d smaller than ksel=%d", who, cap, ksel);
+  MELD_CHECK_ARG(Qn == nullptr || (cap <= K16_ROW_CAPMAX && (cap & 1) == 0), "%s: raw rows have an even stride of at most %d (cap=%d)", who,
+                 K16_ROW_CAPMAX, cap);
+  MELD_CHECK_ARG(err_coef >= 0 && err_coef_lin >= 0, "%s: error coefficients must be non-negative", who);
+  MELD_CHECK_ARG(bw_scale > 0 && bw_scale < INFINITY, "%s: bandwidth_scale must be positive and finite", who);
+  MELD_CHECK_ARG(max_rank == 0 || max_rank > knn, "%s: max_rank=%d must exceed knn=%d (or be 0)", who, max_rank, knn);
+  MELD_HIP_CALL(hipMemsetAsync(cursor, 0, sizeof(int32_t) * (size_t)N, S(stream)));
+  const double rf = pow(-log(thresh), 1.0 / decay);
+  const dim3 grid((unsigned)ceil_div(N, 4));
+  if (Qn == nullptr)
+    hipLaunchKernelGGL((refine_kernel<true, true, false>), grid, dim3(256), 0, S(stream), X, d, (int64_t)0, N, cand_idx, cand_d2, cand_cnt, cand_thr,
+                       ksel, cap, knn, decay, thresh, rf, norm2_max, err_coef, norm2, err_coef_lin, bw_scale, bw_fixed, max_rank, bw,
+                       (double*)nullptr, keep_cnt, flag_rows, n_flag, (const int*)nullptr, 0, (int*)nullptr, cursor, tcol, tval, (int*)nullptr,
+                       (float*)nullptr, (int*)nullptr, (const float*)nullptr, (const float*)nullptr);
+  else
+    hipLaunchKernelGGL((refine_kernel<true, true, true>), grid, dim3(256), 0, S(stream), X, d, (int64_t)0, N, (const int*)nullptr,
+                       (const float*)nullptr, (const int*)nullptr, cand_thr, ksel, cap, knn, decay, thresh, rf, norm2_max, err_coef, norm2,
+                       err_coef_lin, bw_scale, bw_fixed, max_rank, bw, (double*)nullptr, keep_cnt, flag_rows, n_flag, (const int*)nullptr, 0,
+                       (int*)nullptr, cursor, tcol, tval, cand_idx, cand_d2, cand_cnt, Qn, scale_info);
+  MELD_LAUNCH_CHECK("refine_kernel<emit>");
+  return MELD_OK;
+}
+
+extern "C" int meld_knn_refine_emit(const double* X, int64_t N, int d, const int32_t* cand_idx, const float* cand_d2, const int32_t* cand_cnt,
+                                    const float* cand_thr, int ksel, int cap, int knn, double decay, double thresh, const float* norm2_max,
+                                    double err_coef, const float* norm2, double err_coef_lin, double* bw, int32_t* keep_cnt,
+                                    int32_t* flag_rows, int32_t* n_flag, double bw_scale, const double* bw_fixed, int max_rank,
+                                    int32_t* cursor, int32_t* tcol, double* tval, meld_stream_t stream) {
+  return refine_emit_impl("meld_knn_refine_emit", X, N, d, const_cast<int32_t*>(cand_idx), const_cast<float*>(cand_d2),
+                          const_cast<int32_t*>(cand_cnt), nullptr, nullptr, cand_thr, ksel, cap, knn, decay, thresh, norm2_max, err_coef, norm2,
+                          err_coef_lin, bw, keep_cnt, flag_rows, n_flag, bw_scale, bw_fixed, max_rank, cursor, tcol, tval, stream);
+}
+
+// The same on the RAW rows of meld_knn16_topk_listed_raw (cap = meld_knn16_row_capacity(ksel); Qn, scale_info: the search's): every
+// row is ranked in registers as meld_knn16_finish_rows ranks it; only the rows that are flagged are written back finished.
+extern "C" int meld_knn_refine_sort_emit(const double* X, int64_t N, int d, int32_t* cand_idx, float* cand_d2, int32_t* cand_cnt, const float* Qn,
+                                         const float* scale_info, const float* cand_thr, int ksel, int cap, int knn, double decay,
+                                         double thresh, const float* norm2_max, double err_coef, const float* norm2, double err_coef_lin,
+                                         double* bw, int32_t* keep_cnt, int32_t* flag_rows, int32_t* n_flag, double bw_scale,
+                                         const double* bw_fixed, int max_rank, int32_t* cursor, int32_t* tcol, double* tval,
+                                         meld_stream_t stream) {
+  MELD_CHECK_ARG(Qn && scale_info, "meld_knn_refine_sort_emit: null pointer");
+  return refine_emit_impl("meld_knn_refine_sort_emit", X, N, d, cand_idx, cand_d2, cand_cnt, Qn, scale_info, cand_thr, ksel, cap, knn, decay,
+                          thresh, norm2_max, err_coef, norm2, err_coef_lin, bw, keep_cnt, flag_rows, n_flag, bw_scale, bw_fixed, max_rank, cursor,
+                          tcol, tval, stream);
+}
+
 extern "C" int meld_knn_radius_exact(const double* X, int64_t N, int d, int64_t q_begin, const int32_t* flag_rows,
                                      int32_t n_flag, const double* bw, int knn, double decay, double thresh, int mode,
                                      int32_t* fb_cnt, const int64_t* fb_off, int32_t* fb_cursor, int32_t* fb_col,
@@ -561,6 +727,7 @@ extern "C" int meld_knn_radius_exact(const double* X, int64_t N, int d, int64_t 
   if (n_flag == 0) return MELD_OK;
   MELD_CHECK_ARG(bw_scale > 0 && bw_scale < INFINITY, "meld_knn_radius_exact: bandwidth_scale must be positive and finite");
   MELD_CHECK_ARG(X && flag_rows && bw && n_flag > 0 && N > 0 && d > 0, "meld_knn_radius_exact: bad arguments");
+  MELD_CHECK_ARG(!rf_four_chains(d) || ((uintptr_t)X & 15) == 0, "meld_knn_radius_exact: X must be 16-byte aligned (even d <= %d)", RF_DMAX);
   MELD_CHECK_ARG(mode == 0 ? (fb_cnt && err_flag && fb_cursor) : (fb_off && fb_cursor && fb_col && fb_val),
                  "meld_knn_radius_exact: missing output for mode %d", mode);
   const size_t lds = sizeof(double) * RB_FALL * (size_t)d;
@@ -603,6 +770,7 @@ extern "C" int meld_knn_radius_exact(const double* X, int64_t N, int d, int64_t 
 extern "C" int meld_knn_pair_distances(const double* X, int d, const int64_t* rows, const int64_t* cand, int64_t n, int kk, double* out,
                                        meld_stream_t stream) {
   MELD_CHECK_ARG(X && rows && cand && out && d > 0 && n >= 0 && kk > 0, "meld_knn_pair_distances: bad arguments");
+  MELD_CHECK_ARG(!rf_four_chains(d) || ((uintptr_t)X & 15) == 0, "meld_knn_pair_distances: X must be 16-byte aligned (even d <= %d)", RF_DMAX);
   if (n == 0) return MELD_OK;
   hipLaunchKernelGGL(pair_distances_kernel, dim3((unsigned)ceil_div(n * kk, 256)), dim3(256), 0, S(stream), X, d, rows, cand, n, kk, out);
   MELD_LAUNCH_CHECK("pair_distances_kernel");

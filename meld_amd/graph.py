@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from ._lib import check, get_lib, ptr
-from .knn_plan import SearchOptions, plan_knn_search, search_nprod, sphere_layout
+from .knn_plan import SearchOptions, bucket_route, plan_knn_search, search_nprod, sphere_layout
 
 __all__ = ["DeviceGraph", "build_knn_graph", "default_ksel", "EVENTS", "record_events"]
 
@@ -683,7 +683,20 @@ class HipOps:
             raise ValueError("cross search: the queries must lie behind the n_refs references")
         a = SimpleNamespace(X=X, N=N, d=int(X.shape[1]), NR=NR, cross=n_refs is not None, q_begin=q_begin, q_count=q_count, knn=knn, decay=decay,
                             thresh=thresh, bw_scale=bw_scale, bw_fixed=bw_fixed, knn_max=knn_max, force_fallback=force_fallback,
-                            col_stats=col_stats, frame_axes=frame_axes, tm=tm or _Timer(False))
+                            col_stats=col_stats, frame_axes=frame_axes, tm=tm or _Timer(False), assemble=bool(assemble), rows_fused=True)
+        out = self._directed_kernel(a, ksel, comm, assemble, symm, count_rows_ge, anisotropy)
+        if out is None:
+            # The fused row pass (plan.fused_rows) sent the rows to buckets that cannot be finished -- a hub cell with more entries
+            # than a bucket holds, or a column three times in a row -- and kept no kernel values for the sort-based assembly: the
+            # graph is built again with the three row kernels.  Rare; the same graph as if the fused pass had never been planned.
+            a.rows_fused = False
+            out = self._directed_kernel(a, ksel, comm, assemble, symm, count_rows_ge, anisotropy)
+            out[3]["fused_rows_recovered"] = True
+        return out
+
+    def _directed_kernel(self, a, ksel, comm, assemble, symm, count_rows_ge, anisotropy):
+        """The stages of ``directed_kernel_coo``; None where the fused row pass ended in buckets that cannot be finished."""
+        q_count, force_fallback = a.q_count, a.force_fallback
         r = self._search_and_refine(a, ksel, comm)
         retry_from = None
         if r.n_flag > max(1024, q_count // 100) and ksel < 128 and r.plan.search == "f16x3" and not force_fallback:
@@ -696,8 +709,11 @@ class HipOps:
             r = self._search_and_refine(a, ksel, None)
         s = self._exact_sweep(a, r, count_rows_ge)
         keys, vals, assembled = self._emit(a, r, s, ksel, assemble, symm, anisotropy)
+        if r.buckets is not None and assembled is None and r.m_main + s.fb_total > 0:
+            return None
         p, c = r.plan, r.cands
         info = dict(ksel=int(ksel), KP=int(c.KP), search=p.search, nprod=p.nprod, n_flagged_rows=r.n_flag,
+                    fused_rows=p.fused_rows if p.fused_rows != "sort+emit" or getattr(c, "raw", None) is not None else "emit",
                     # the route the search took (meld_amd.knn_plan.KnnPlan)
                     prune=p.prune, radius_cut=p.radius_cut, seed=p.seed != "none", seeded_bounds=p.seeded_bounds, block_order=p.block_order != "none",
                     step_lists=p.lists != "none", principal_frame=p.frame, two_phase=p.two_pass, n_rows_bandwidth_recomputed=s.n_rebandwidth,
@@ -719,7 +735,9 @@ class HipOps:
         nprod = search_nprod(self.nprod, a.d)
         resident = lib.meld_knn16_resident_blocks(a.d, nprod) if lib.meld_knn16_kblocks(a.d) > 0 and nprod in (1, 3) else 0
         plan = plan_knn_search(lib, a.N, a.d, a.q_begin, a.q_count, a.knn, ksel, options=self, cross=a.cross, bandwidth=a.bw_fixed is not None,
-                               world=getattr(comm, "world", 1) if comm is not None else 1, resident=resident)
+                               world=getattr(comm, "world", 1) if comm is not None else 1, resident=resident,
+                               assemble=a.assemble and a.rows_fused, free_bytes=torch.cuda.mem_get_info(dev)[0] if a.assemble and a.rows_fused else 0,
+                               x_aligned=a.X.data_ptr() % 16 == 0)
         a.tm.start()
         col_min = col_max = None
         if a.col_stats is not None:  # (the front end's pass over X -- its NaN / infinity check -- already has them)
@@ -965,7 +983,14 @@ class HipOps:
                        torch.empty(S * q_pad, dtype=torch.int32, device=dev), torch.full((S, q_pad), float("inf"), dtype=torch.float32, device=dev))
             else:
                 out = (c.idx, c.d2, c.cnt, c.thr)
-            if step_list is not None:
+            c.raw = None
+            if step_list is not None and plan.fused_rows == "sort+emit" and S == 1:
+                # the rows stay as the search leaves them: the refinement ranks them in registers (meld_knn_refine_sort_emit)
+                check(lib.meld_knn16_topk_listed_raw(ptr(o.Q), ptr(o.Qn), ptr(o.Rt), ptr(o.scale_info), a.NR, d, q_count, ksel, ptr(step_list), ptr(step_cnt),
+                                                     o.n_tiles, ptr(c.nmax), q0, ptr(seeds), plan.knn_cut, rfac, *map(ptr, out), ptr(tiles_b), ptr(block_order),
+                                                     int(plan.partial_in_search), st), "meld_knn16_topk_listed_raw")
+                c.raw = (o.Qn, o.scale_info)
+            elif step_list is not None:
                 check(lib.meld_knn16_topk_listed_partial(ptr(o.Q), ptr(o.Qn), ptr(o.Rt), ptr(o.scale_info), a.NR, d, q_count, ksel, ptr(step_list), ptr(step_cnt),
                                                          o.n_tiles, ptr(c.nmax), q0, ptr(seeds), plan.knn_cut, rfac, *map(ptr, out), ptr(tiles_b), ptr(block_order),
                                                          S, int(plan.partial_in_search), st), "meld_knn16_topk_listed")
@@ -992,21 +1017,37 @@ class HipOps:
         r = SimpleNamespace(plan=c.plan, cands=c)
         max_rank = 0 if a.knn_max is None else int(a.knn_max) + 1  # (self counted, as graphtools counts it)
         r.bw = torch.empty(q_count, dtype=torch.float64, device=dev)
-        r.cand_val = torch.empty(q_count * ksel, dtype=torch.float64, device=dev)
         r.keep_cnt = torch.empty(q_count, dtype=torch.int32, device=dev)
         r.flag_rows = torch.empty(q_count, dtype=torch.int32, device=dev)
         n_flag = torch.zeros(1, dtype=torch.int32, device=dev)
         nmax_used = c.nmax
         if a.force_fallback:  # test hook: an infinite error bound flags every row
             nmax_used = torch.full((1,), float("inf"), dtype=torch.float32, device=dev)
-        check(
-            lib.meld_knn_refine(
-                ptr(a.X), a.N, a.d, a.q_begin, q_count, ptr(c.idx), ptr(c.d2), ptr(c.cnt), ptr(c.thr), ksel, c.cap, a.knn, float(a.decay),
-                float(a.thresh), ptr(nmax_used), float(c.err_coef), ptr(c.norm2), float(c.err_lin), ptr(r.bw), ptr(r.cand_val), ptr(r.keep_cnt),
-                ptr(r.flag_rows), ptr(n_flag), None, 0, None, float(a.bw_scale), ptr(a.bw_fixed), max_rank, st,
-            ),
-            "meld_knn_refine",
-        )
+        r.buckets = r.cand_val = r.rows2 = None
+        if c.plan.fused_rows != "off":
+            # the kept entries of the complete rows go straight into the row buckets (cursor, tcol, tval); kernel values are stored
+            # for the rows of the second stage only (_stage2), which _emit sends behind them with the swept entries
+            B = int(lib.meld_csr_bucket_slots())
+            r.buckets = (torch.empty(q_count, dtype=torch.int32, device=dev), torch.empty(q_count * B, dtype=torch.int32, device=dev),
+                         torch.empty(q_count * B, dtype=torch.float64, device=dev))
+            raw = getattr(c, "raw", None)  # (the search left the rows raw: ranked inside the refinement)
+            tail = (ksel, c.cap, a.knn, float(a.decay), float(a.thresh), ptr(nmax_used), float(c.err_coef), ptr(c.norm2), float(c.err_lin), ptr(r.bw),
+                    ptr(r.keep_cnt), ptr(r.flag_rows), ptr(n_flag), float(a.bw_scale), ptr(a.bw_fixed), max_rank, *map(ptr, r.buckets), st)
+            if raw is not None:
+                check(lib.meld_knn_refine_sort_emit(ptr(a.X), a.N, a.d, ptr(c.idx), ptr(c.d2), ptr(c.cnt), ptr(raw[0]), ptr(raw[1]), ptr(c.thr), *tail),
+                      "meld_knn_refine_sort_emit")
+            else:
+                check(lib.meld_knn_refine_emit(ptr(a.X), a.N, a.d, ptr(c.idx), ptr(c.d2), ptr(c.cnt), ptr(c.thr), *tail), "meld_knn_refine_emit")
+        else:
+            r.cand_val = torch.empty(q_count * ksel, dtype=torch.float64, device=dev)
+            check(
+                lib.meld_knn_refine(
+                    ptr(a.X), a.N, a.d, a.q_begin, q_count, ptr(c.idx), ptr(c.d2), ptr(c.cnt), ptr(c.thr), ksel, c.cap, a.knn, float(a.decay),
+                    float(a.thresh), ptr(nmax_used), float(c.err_coef), ptr(c.norm2), float(c.err_lin), ptr(r.bw), ptr(r.cand_val), ptr(r.keep_cnt),
+                    ptr(r.flag_rows), ptr(n_flag), None, 0, None, float(a.bw_scale), ptr(a.bw_fixed), max_rank, st,
+                ),
+                "meld_knn_refine",
+            )
         r.n_flag = r.n_flag_stage1 = int(n_flag.item())
         a.tm.stop("refine")
         stage2 = c.research is not None and r.n_flag > 0 and not a.force_fallback
@@ -1032,6 +1073,9 @@ class HipOps:
         lib, st, dev, d, cap, o = self.lib, _stream(), a.X.device, a.d, c.cap, c.research
         n_flag_h = r.n_flag
         rows2 = torch.sort(r.flag_rows[:n_flag_h]).values.contiguous()
+        if r.buckets is not None:  # (fused row pass: the first stage stored no kernel values; these rows' are stored at their local row)
+            r.cand_val = torch.empty(a.q_count * ksel, dtype=torch.float64, device=dev)
+            r.rows2 = rows2
         q2_pad = ((n_flag_h + o.BQ - 1) // o.BQ) * o.BQ
         Q2 = torch.empty(q2_pad * lib.meld_knn16_query_bytes(d), dtype=torch.uint8, device=dev)
         Qn2 = torch.empty(q2_pad, dtype=torch.float32, device=dev)
@@ -1145,22 +1189,36 @@ class HipOps:
         """The kept entries as (keys, vals) COO pairs -- or, on a single GPU with every row local, straight into the row buckets of
         the symmetrisation (meld_coo_emit_scatter) instead of through 2 M (key, value) pairs (512 MB written and read back at 1M
         cells).  Returns (keys, vals, assembled): assembled = (rowptr, col, val[, row sums[, degrees]]) of the symmetrised rows, else
-        None; with the degrees (``anisotropy`` given), val is the kernel with the anisotropy applied."""
+        None; with the degrees (``anisotropy`` given), val is the kernel with the anisotropy applied.  On the fused route
+        (``plan.fused_rows``) the refinement has filled the buckets with the complete rows already: the rows of the second stage and
+        the swept entries follow (meld_coo_emit_scatter_listed); buckets that cannot be finished then return (None, None, None)."""
         lib, st, dev, q_count, n_flag_h, c = self.lib, _stream(), a.X.device, a.q_count, r.n_flag, r.cands
         M = r.m_main + s.fb_total
         assembled = None
-        if assemble and M > 0 and a.q_begin == 0 and q_count == a.NR and not a.cross and opt("MELD_ASSEMBLE", "bucket") == "bucket" \
-                and opt("MELD_ASSEMBLE_FUSED", "1") != "0":
-            B = int(lib.meld_csr_bucket_slots())
-            if ksel <= B and q_count * B * 12 <= torch.cuda.mem_get_info(dev)[0] // 4:
-                cursor = r.keep_cnt.clone()
-                if n_flag_h > 0 and s.fb_total > 0:
-                    cursor[r.flag_rows[:n_flag_h].to(torch.int64)] = s.fb_cnt
-                tcol = torch.empty(q_count * B, dtype=torch.int32, device=dev)
-                tval = torch.empty(q_count * B, dtype=torch.float64, device=dev)
-                check(lib.meld_coo_emit_scatter(q_count, ptr(c.idx), ptr(r.cand_val), ksel, c.cap, ptr(r.keep_cnt), ptr(r.flag_rows), n_flag_h,
-                                                ptr(s.fb_off), ptr(s.fb_col), ptr(s.fb_val), s.fb_total, ptr(cursor), ptr(tcol), ptr(tval), st),
-                      "meld_coo_emit_scatter")
+        # (plan.fused_rows: the refinement filled the buckets with the complete rows; meld_amd.metric_knn hands in rows of its own)
+        fused = getattr(r, "buckets", None) is not None
+        if fused or (M > 0 and bucket_route(lib, a.NR, a.q_begin, q_count, ksel, cross=a.cross, assemble=assemble,
+                                            free_bytes=torch.cuda.mem_get_info(dev)[0])):
+            if fused and M == 0:
+                r.buckets = None
+            else:
+                if fused:
+                    cursor, tcol, tval = r.buckets
+                    n2 = int(r.rows2.shape[0]) if r.rows2 is not None else 0
+                    if n2 > 0 or (n_flag_h > 0 and s.fb_total > 0):  # the rows of the second stage, the entries of the sweep
+                        check(lib.meld_coo_emit_scatter_listed(ptr(r.rows2), n2, ptr(c.idx), ptr(r.cand_val), ksel, c.cap, ptr(r.keep_cnt), ptr(r.flag_rows),
+                                                               n_flag_h, ptr(s.fb_off), ptr(s.fb_col), ptr(s.fb_val), s.fb_total, ptr(cursor), ptr(tcol),
+                                                               ptr(tval), st), "meld_coo_emit_scatter_listed")
+                else:
+                    B = int(lib.meld_csr_bucket_slots())
+                    cursor = r.keep_cnt.clone()
+                    if n_flag_h > 0 and s.fb_total > 0:
+                        cursor[r.flag_rows[:n_flag_h].to(torch.int64)] = s.fb_cnt
+                    tcol = torch.empty(q_count * B, dtype=torch.int32, device=dev)
+                    tval = torch.empty(q_count * B, dtype=torch.float64, device=dev)
+                    check(lib.meld_coo_emit_scatter(q_count, ptr(c.idx), ptr(r.cand_val), ksel, c.cap, ptr(r.keep_cnt), ptr(r.flag_rows), n_flag_h,
+                                                    ptr(s.fb_off), ptr(s.fb_col), ptr(s.fb_val), s.fb_total, ptr(cursor), ptr(tcol), ptr(tval), st),
+                          "meld_coo_emit_scatter")
                 a.tm.stop("coo_emit")
                 # MELD_ASSEMBLE_FUSED_ANISO=0: the anisotropy as a pass of its own over the finished CSR (same bits)
                 aniso = anisotropy if opt("MELD_ASSEMBLE_FUSED_ANISO", "1") != "0" else None
@@ -1171,6 +1229,8 @@ class HipOps:
                         assembled = assembled + (self.last_degrees,)
                 a.tm.stop("symmetrize")
                 del cursor, tcol, tval
+                if fused and assembled is None:
+                    return None, None, None  # (no kernel values to fall back on: directed_kernel_coo builds the graph again)
         keys = vals = None
         if assembled is None:
             keys = torch.empty(2 * M, dtype=torch.int64, device=dev)

@@ -78,6 +78,10 @@ class KnnPlan:
     # (how the operands are written, not which route the search takes: same bits either way, so two plans that differ in this alone
     # compare equal)
     fused_operands: bool = dataclasses.field(default=False, compare=False)
+    # the row passes behind the search: "off" (finish, refinement and emit as three kernels), "emit" (the refinement sends the
+    # kept entries of complete rows straight to the row buckets, meld_knn_refine_emit) or "sort+emit" (it also takes the rows raw
+    # from the search and ranks them in registers, meld_knn_refine_sort_emit); same graph bit for bit
+    fused_rows: str = dataclasses.field(default="off", compare=False)
 
     def __post_init__(self):
         if self.lead_bounds is None:
@@ -103,12 +107,43 @@ def sphere_layout(lib, N, d):
     return int(rows.value), int(row_bytes.value)
 
 
-def plan_knn_search(lib, N, d, q_begin, q_count, knn, ksel, *, options, cross=False, bandwidth=False, world=1, resident=0):
+def bucket_route(lib, N, q_begin, q_count, ksel, *, cross, assemble, free_bytes):
+    """Whether the kept entries go straight into the row buckets of the symmetrisation (``HipOps._emit``), as far as that is known
+    before the search: a single GPU that holds every row and is asked for the assembled rows, the bucket assembly selected, a
+    candidate list that fits a bucket, and a quarter of the free memory (``free_bytes``) enough for the buckets."""
+    if not assemble or cross or q_begin != 0 or q_count != N:
+        return False
+    if opt("MELD_ASSEMBLE", "bucket") != "bucket" or opt("MELD_ASSEMBLE_FUSED", "1") == "0":
+        return False
+    B = int(lib.meld_csr_bucket_slots())
+    return ksel <= B and q_count * B * 12 <= int(free_bytes) // 4
+
+
+def plan_fused_rows(lib, N, d, q_begin, q_count, ksel, *, search, cross=False, world=1, assemble=False, free_bytes=0, x_aligned=True,
+                    raw_rows=False):
+    """"emit" where the refinement may send its rows straight to the buckets (``meld_knn_refine_emit``), else "off": the bucket
+    route, the split-fp16 search, the four-chain refinement (even d <= 256, rows 16-byte aligned) and a list of at most two entries
+    per lane.  "sort+emit" where the search can also leave its rows raw (``raw_rows``: the list-driven first pass in one slice --
+    sliced searches are merged into finished rows).  MELD_ROWS_FUSED (development) = 0: always the three kernels, a: "emit" at most."""
+    if search != "f16x3" or world != 1 or not bucket_route(lib, N, q_begin, q_count, ksel, cross=cross, assemble=assemble, free_bytes=free_bytes):
+        return "off"
+    if d % 2 != 0 or d > 256 or not x_aligned or ksel > 128 or ksel > int(lib.meld_csr_bucket_slots()):
+        return "off"
+    want = opt("MELD_ROWS_FUSED", "b")
+    if want == "0":
+        return "off"
+    return "sort+emit" if raw_rows and want != "a" else "emit"
+
+
+def plan_knn_search(lib, N, d, q_begin, q_count, knn, ksel, *, options, cross=False, bandwidth=False, world=1, resident=0, assemble=False,
+                    free_bytes=0, x_aligned=True):
     """Route of ``directed_kernel_coo`` for rows [q_begin, q_begin + q_count) of N cells in d dimensions.
 
     ``options``: a ``SearchOptions`` (or ``HipOps``); ``cross``: a search between two point sets (``n_refs``); ``bandwidth``: the
     kernel radius is given; ``world``: ranks that share the tile spheres (1: none); ``resident``: workgroups of the search
-    resident on the device at once (``meld_knn16_resident_blocks(d, search_nprod(nprod, d))``, the one query that needs a device)."""
+    resident on the device at once (``meld_knn16_resident_blocks(d, search_nprod(nprod, d))``, the one query that needs a device);
+    ``assemble`` / ``free_bytes`` / ``x_aligned``: the caller wants the assembled rows, the device's free memory, the cells are
+    16-byte aligned -- what ``plan_fused_rows`` decides the row passes behind the search on."""
     search = options.search
     if search == "f16x3" and lib.meld_knn16_kblocks(d) < 0:
         search = "wide"  # d beyond the instantiated MFMA kernels (d > 141)
@@ -161,5 +196,7 @@ def plan_knn_search(lib, N, d, q_begin, q_count, knn, ksel, *, options, cross=Fa
     # One pass over the cells for both operand layouts and the tile spheres where the queries are all the references and the
     # spheres are wanted here (pruned, not shared between ranks).  MELD_KNN_FUSED_OPERANDS=0: the three separate passes (same bits).
     fused = prune and bounds != "bounds_from_spheres" and q_begin == 0 and q_count == N and opt("MELD_KNN_FUSED_OPERANDS", "1") != "0"
+    fused_rows = plan_fused_rows(lib, N, d, q_begin, q_count, ksel, search=search, cross=cross, world=world, assemble=assemble,
+                                 free_bytes=free_bytes, x_aligned=x_aligned, raw_rows=lists != "none" and main_slices == 1)
     return KnnPlan(search, nprod, frame, radius_cut, prune, seed, 0 if seed == "bandwidth" else knn, bounds, seeded_bounds, lists,
-                   block_order, main_slices, two_pass, partial, nprod == 1, lead_bounds, ee is not None, fused)
+                   block_order, main_slices, two_pass, partial, nprod == 1, lead_bounds, ee is not None, fused, fused_rows)
