@@ -811,6 +811,39 @@ int meld_indicator_signal(const int64_t* codes, const double* scale, const int64
  * (meld/meld.py:246-250 wraps them with the labels' index). */
 int meld_scatter_rows_f64(const double* in, const int64_t* perm, int64_t n_rows, int p, double* out, meld_stream_t stream);
 
+/* ---- connectivity (csrc/components.hip; replaces [UPSTREAM pygsp Graph.is_connected / extract_components / subgraph] and
+ *      scipy.sparse.csgraph.connected_components on the exported W) ----------------------------------------------------------
+ * The operand is the CSR of a single-GPU graph: W symmetric without diagonal, rowptr[n_rows + 1] int64, col[nnz] int32 in
+ * [0, n_rows), rows in device order; 1 <= n_rows < 2^31 everywhere.  Integer atomics only: the same output every run.
+ *
+ * meld_cc_round: one round of hook-and-compress on parent[n_rows] (int32; the caller starts it at parent[v] = v).  Hook: every
+ *   row tries atomicMin(parent[root of the row], min of parent[] over its columns); compress: every vertex stores the ancestor
+ *   its chain leads to.  parent[v] <= v always and values only decrease, so chains descend and every chase ends (each is capped
+ *   at 64 loads besides).  *changed (device word) is cleared first and set to 1 when the round stored anything.  The caller
+ *   repeats rounds until one leaves *changed == 0: then parent[v] is the smallest device index of v's component.  Launch ends
+ *   are the only synchronisation between workgroups.  col may be NULL for a graph without entries.
+ * meld_cc_minima (parents at their fixed point): min_orig[r] = the smallest caller-order index of root r's component (perm[v]
+ *   for device row v, v itself where perm is NULL), count[r] = its size (both int32 [n_rows], defined at roots only), and
+ *   flags[i] = 1 where i is such a minimum, 0 elsewhere (int32 [n_rows]: the input of meld_exclusive_scan_i32_i64, whose output
+ *   is `rank`, rank[n_rows] the number of components).
+ * meld_cc_labels: labels[perm[v]] = rank[min_orig[parent[v]]] (int32 [n_rows], the caller's order: components numbered by their
+ *   smallest caller-order index, as scipy numbers them) and sizes[label] = count (int64 [number of components]). */
+int meld_cc_round(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int32_t* parent, int32_t* changed,
+                  meld_stream_t stream);
+int meld_cc_minima(const int32_t* parent, const int64_t* perm, int64_t n_rows, int32_t* min_orig, int32_t* count, int32_t* flags,
+                   meld_stream_t stream);
+int meld_cc_labels(const int32_t* parent, const int64_t* perm, const int32_t* min_orig, const int32_t* count, const int64_t* rank,
+                   int64_t n_rows, int32_t* labels, int64_t* sizes, meld_stream_t stream);
+/* Induced subgraph.  new_index[n_rows] (int32, device order): the new row / column number of a kept vertex, -1 for a dropped
+ * one; kept vertices are numbered in ascending device order, so the kept columns of a row stay sorted.
+ * meld_subgraph_count: counts[new_index[u]] = kept entries of kept row u (int32 [number kept]; scanned by the caller into
+ *   sub_rowptr).  meld_subgraph_fill: sub_col / sub_val [sub_rowptr[number kept]] = the kept entries, columns renumbered, values
+ *   copied bit for bit. */
+int meld_subgraph_count(const int64_t* rowptr, const int32_t* col, const int32_t* new_index, int64_t n_rows, int32_t* counts,
+                        meld_stream_t stream);
+int meld_subgraph_fill(const int64_t* rowptr, const int32_t* col, const double* val, const int32_t* new_index, int64_t n_rows,
+                       const int64_t* sub_rowptr, int32_t* sub_col, double* sub_val, meld_stream_t stream);
+
 /* ---- next#1: normalize_densities (meld/utils.py:35-47) ------------------------------------ */
 /* out[i,:] = in[i,:] / sum_j |in[i,j]|  (rows of zeros are copied unchanged, as sklearn does) */
 int meld_normalize_rows_l1(const double* in, double* out, int64_t n_rows, int p, meld_stream_t stream);

@@ -184,6 +184,11 @@ SIGNATURES = {
     "meld_factorize_codes": (_i32, [_ptr, _i64, _ptr, _ptr, _ptr]),
     "meld_indicator_signal": (_i32, [_ptr, _ptr, _ptr, _i64, _i64, _i32, _ptr, _ptr]),
     "meld_scatter_rows_f64": (_i32, [_ptr, _ptr, _i64, _i32, _ptr, _ptr]),
+    "meld_cc_round": (_i32, [_ptr, _ptr, _i64, _ptr, _ptr, _ptr]),
+    "meld_cc_minima": (_i32, [_ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "meld_cc_labels": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr]),
+    "meld_subgraph_count": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr]),
+    "meld_subgraph_fill": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
 }
 
 

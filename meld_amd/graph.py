@@ -504,6 +504,62 @@ class DeviceGraph:
             raise ValueError("transform must have one row per fitted cell ({}), got shape {}".format(self.N, tuple(F.shape)))
         return extend.apply_transitions(self.kernel_to_data_device(Y), F.to(torch.float64), colmap=colmap)
 
+    # -- connectivity (meld_amd/components.py, csrc/components.hip): pygsp's ``is_connected`` / ``extract_components`` / ``subgraph``,
+    # scipy's labels.  Single-GPU graphs; nothing goes through the host but the counts. ---------------------------------------------
+    def connected_components_device(self, recompute=False, max_rounds=None):
+        """``(n_components, labels)``: ``labels`` an int32 device tensor ``[N]`` in the caller's cell order, equal to
+        ``scipy.sparse.csgraph.connected_components(G.W, directed=False)`` (components numbered by their smallest cell).
+        Hook-and-compress rounds on the device until one writes nothing; RuntimeError, naming the rounds done, after ``max_rounds``
+        (default ``4 ceil(log2 N) + 64``).  Kept on the graph; ``components_info`` is ``dict(rounds, n_components, largest)``."""
+        from . import components
+
+        return components.connected_components_device(self, recompute=recompute, max_rounds=max_rounds)
+
+    def connected_components(self):
+        """``connected_components_device`` with the labels as a host int32 array: scipy's return value."""
+        n, labels = self.connected_components_device()
+        return n, labels.cpu().numpy()
+
+    @property
+    def component_sizes(self):
+        """Cells per component (host int64 ``[n_components]``, in label order)."""
+        self.connected_components_device()
+        return self._components["sizes"]
+
+    def is_connected(self, recompute=False):
+        """[UPSTREAM pygsp ``Graph.is_connected``]: one component."""
+        return self.connected_components_device(recompute=recompute)[0] == 1
+
+    def subgraph(self, ind):
+        """[UPSTREAM pygsp ``Graph.subgraph``]: the graph induced by the cells ``ind`` -- an integer array or a boolean mask, on
+        the host or the device.  Cell ``i`` of the result is ``ind[i]``; its device order is this graph's restricted to the kept
+        cells, so it carries a ``perm`` of its own unless that is the identity.  Weights are copied bit for bit, degrees summed
+        anew.  ValueError for duplicates, indices out of range and an empty selection, TypeError for other dtypes.  Carried over:
+        ``info["orig_idx"]`` (host int64), the kept cells' kernel diagonal (``K`` / ``diff_op`` are this graph's kernel restricted
+        to them), ``bandwidth``, ``info["knn"]``.  Not carried: ``lmax``, the Fourier caches, the tiled layout, the state of the
+        out-of-sample extension."""
+        from . import components
+
+        return components.subgraph(self, ind)
+
+    def extract_components(self):
+        """[UPSTREAM pygsp ``Graph.extract_components``]: one subgraph per component, in label order, ``info["component"]`` set.
+        A plain loop over ``subgraph``: one pass over this graph's CSR per component."""
+        n, labels = self.connected_components_device()
+        out = []
+        for c in range(n):
+            sub = self.subgraph(torch.nonzero(labels == c)[:, 0])
+            sub.info["component"] = c
+            out.append(sub)
+        return out
+
+    def largest_component(self):
+        """The subgraph of the component with the most cells (the lowest label among equals), ``info["component"]`` set."""
+        c = int(np.argmax(self.component_sizes))
+        sub = self.subgraph(torch.nonzero(self._components["labels"] == c)[:, 0])
+        sub.info["component"] = c
+        return sub
+
 
 _BLAS_CTL = None
 
