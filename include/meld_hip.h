@@ -844,6 +844,27 @@ int meld_subgraph_count(const int64_t* rowptr, const int32_t* col, const int32_t
 int meld_subgraph_fill(const int64_t* rowptr, const int32_t* col, const double* val, const int32_t* new_index, int64_t n_rows,
                        const int64_t* sub_rowptr, int32_t* sub_col, double* sub_val, meld_stream_t stream);
 
+/* ---- diffusion of cell signals (csrc/diffuse.hip; replaces the product with graphtools' diff_op = normalize(K, "l1", axis=1)
+ *      that [UPSTREAM magic-impute, unpinned: not importable next to this code] repeats t times) ------------------------------
+ * One step of the random walk of the kernel matrix K = W + diag(kd) on a wide fp64 signal, rows in the graph's device order:
+ *     y[i, c] = ( sum_{e in row i, storage order} val[e] * x[col[e], c]  +  kd[i] * x[i, c] ) / s[i]         c < p
+ * rowptr[n_rows + 1] int64, col[nnz] int32 in [0, n_rows), val[nnz] fp64: the CSR of W (no diagonal); kd[n_rows] the kernel's
+ * diagonal, s[n_rows] = dw + kd the row sums of K (s[i] != 0 is the caller's to check: the kernel divides).
+ * x and y are [n_rows, ld] row-major with ldx, ldy >= p (in doubles); columns beyond p are neither read nor written, so a
+ * wider signal is processed in column panels without copies.  1 <= p <= meld_diffuse_max_cols() = 128 per call; lanes =
+ * columns, with p > 64 a lane carries column `lane` and column `lane + 64` (8-byte accesses only: x, y and the leading
+ * dimensions need no alignment beyond 8 bytes).  The matrix is streamed once per call, whatever p.
+ * One output element is: acc = 0; acc = fma(val[e], x[col[e], c], acc) over the row's entries in storage order;
+ * acc = fma(kd[i], x[i, c], acc); one true division by s[i] -- a function of the operands alone: the other columns of the launch,
+ * p, the panel, the leading dimensions and the run do not change a bit of it.  No atomics.  A row without entries gives
+ * kd x / s.
+ * y must not overlap x: a call whose ranges [x, x + n_rows*ldx) and [y, y + n_rows*ldy) intersect returns -1.  So do, before any
+ * launch: a NULL rowptr / kd / s / x / y; a NULL col or val for a matrix with rows (one without entries passes any address: they
+ * are not read); p out of range; ld < p; n_rows < 0.  n_rows == 0 is a successful no-op. */
+int meld_diffuse_max_cols(void);
+int meld_diffuse_step(const int64_t* rowptr, const int32_t* col, const double* val, const double* kd, const double* s,
+                      int64_t n_rows, const double* x, int64_t ldx, double* y, int64_t ldy, int p, meld_stream_t stream);
+
 /* ---- next#1: normalize_densities (meld/utils.py:35-47) ------------------------------------ */
 /* out[i,:] = in[i,:] / sum_j |in[i,j]|  (rows of zeros are copied unchanged, as sklearn does) */
 int meld_normalize_rows_l1(const double* in, double* out, int64_t n_rows, int p, meld_stream_t stream);

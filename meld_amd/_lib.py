@@ -189,6 +189,8 @@ SIGNATURES = {
     "meld_cc_labels": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr]),
     "meld_subgraph_count": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr]),
     "meld_subgraph_fill": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "meld_diffuse_max_cols": (_i32, []),
+    "meld_diffuse_step": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _ptr]),
 }
 
 

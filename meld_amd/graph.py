@@ -504,6 +504,24 @@ class DeviceGraph:
             raise ValueError("transform must have one row per fitted cell ({}), got shape {}".format(self.N, tuple(F.shape)))
         return extend.apply_transitions(self.kernel_to_data_device(Y), F.to(torch.float64), colmap=colmap)
 
+    # -- diffusion of cell signals (meld_amd/diffuse.py, csrc/diffuse.hip): ``diff_op`` applied on the device, never formed --------
+    def diffuse_device(self, F, t=1, device_order=False):
+        """``diff_op^t F`` as an fp64 device tensor ``[N, p]`` (``[N]`` for 1-D input): ``t`` steps of the random walk of the
+        kernel matrix, ``y = (W x + kd .* x) / (dw + kd)``, on a device tensor, a host array or a DataFrame with one row per cell.
+        Rows in the caller's order unless ``device_order`` (as in ``interpolate_device``: then neither the input nor the output is
+        permuted).  ``t = 0`` returns a copy.  Signals wider than 128 columns go through the kernel panel by panel; a column's
+        values do not depend on the other columns.  ValueError on a row-sharded graph and where a cell's kernel row sum is not
+        positive (an adopted graph with an isolated vertex and a zero kernel diagonal); ``t="auto"`` is not implemented."""
+        from . import diffuse
+
+        return diffuse.diffuse_device(self, F, t=t, device_order=device_order)
+
+    def diffuse(self, F, t=1):
+        """``diffuse_device`` as a host ndarray; a DataFrame comes back as a DataFrame with its index and columns."""
+        from . import diffuse
+
+        return diffuse.diffuse(self, F, t=t)
+
     # -- connectivity (meld_amd/components.py, csrc/components.hip): pygsp's ``is_connected`` / ``extract_components`` / ``subgraph``,
     # scipy's labels.  Single-GPU graphs; nothing goes through the host but the counts. ---------------------------------------------
     def connected_components_device(self, recompute=False, max_rounds=None):

@@ -461,6 +461,41 @@ class MELD(GraphEstimator):
         index = Y.index if isinstance(Y, (pd.DataFrame, pd.Series)) else None
         return pd.DataFrame(values, index=index, columns=self.sample_densities.columns)
 
+    def fit(self, X, **kwargs):
+        """``GraphEstimator.fit``; where ``X`` is a DataFrame its column names and index are kept with the graph's model of the
+        data (``impute`` labels its result with them)."""
+        super().fit(X, **kwargs)
+        st = getattr(self.graph, "_extend_state", None)
+        if st is not None and not getattr(self, "_graph_precomputed", False):  # (a graph handed to fit keeps what it came with)
+            frame = isinstance(X, pd.DataFrame)
+            st.columns = X.columns if frame else None
+            st.index = X.index if frame else None
+        return self
+
+    def impute(self, genes=None, t=3):
+        """MAGIC's approximate solver on the fitted graph ([UPSTREAM magic-impute ``MAGIC.fit_transform(data, genes=...)``,
+        unpinned: it cannot be imported next to this code]): the matrix the graph was searched on (the PCA or SVD scores, or the
+        data where ``fit`` reduced nothing) is diffused ``t`` times with the graph's ``diff_op`` on the device and mapped back to
+        the requested columns of the data ``fit`` saw -- ``X_t V[genes].T + mean[genes]`` (PCA), ``X_t V[genes].T`` (the uncentred
+        SVD of sparse input), the columns themselves without a reduction -- by one GEMM.
+
+        ``genes``: integers, a boolean mask over the columns, names (where ``fit`` received a DataFrame), or None for every
+        column.  ``t``: an integer >= 0 (``"auto"`` is not implemented).  Returns a DataFrame ``[N, len(genes)]`` with the cells'
+        index and the genes' names (the integers where ``fit`` saw no names).  NotImplementedError, naming the case, for a graph
+        that keeps no cells (``fit(G)``, adopted graphs, precomputed matrices), for the metrics that transform the rows (cosine,
+        correlation) and for a row-sharded graph.  For any other per-cell signal -- raw marker genes, densities -- call
+        ``op.graph.diffuse(signal, t)``."""
+        from . import diffuse
+
+        if self.graph is None:
+            raise ValueError("Estimator must be `fit` before running `impute`.")
+        if not hasattr(self.graph, "diffuse_device"):
+            raise NotImplementedError("the graph of this estimator cannot diffuse a signal")
+        values, idx = diffuse.impute(self.graph, genes=genes, t=t)
+        st = self.graph._extend_state
+        columns = idx if getattr(st, "columns", None) is None else st.columns[idx]
+        return pd.DataFrame(values.cpu().numpy(), index=getattr(st, "index", None), columns=columns)
+
     def fit_transform(self, X, sample_labels, **kwargs):
         """Builds the graph on ``X`` and estimates the density of each sample in
         ``sample_labels`` (reference ``meld/meld.py:252-274``)."""
