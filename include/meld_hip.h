@@ -865,6 +865,40 @@ int meld_diffuse_max_cols(void);
 int meld_diffuse_step(const int64_t* rowptr, const int32_t* col, const double* val, const double* kd, const double* s,
                       int64_t n_rows, const double* x, int64_t ldx, double* y, int64_t ldy, int p, meld_stream_t stream);
 
+/* ---- geodesic distances (csrc/geodesic.hip; replaces scipy.sparse.csgraph.dijkstra on the exported graph, what [UPSTREAM
+ *      graphtools 1.5.x BaseGraph.shortest_path, unpinned: not importable next to this code] calls) ---------------------------
+ * meld_minplus_step: one synchronous Bellman-Ford round on a row-major fp64 distance block, rows in the graph's device order:
+ *     y[i, c] = min( x[i, c],  min_{e in row i} ( x[col[e], c] + len[e] ) )                                c < p
+ * rowptr[n_rows + 1] int64, col[nnz] int32 in [0, n_rows): the CSR of W; len[nnz] fp64, finite and >= 0, aligned with col (the
+ * solver presumes len symmetric).  x holds distances >= 0 or +inf ("not reached": inf + len = inf); with such operands no NaN
+ * arises -- validating them is the caller's (meld_amd/geodesic.py does).
+ * x and y are [n_rows, ld] row-major with ldx, ldy >= p (in doubles); columns beyond p are neither read nor written, so a wider
+ * source set is processed in column panels without copies.  1 <= p <= meld_minplus_max_cols() = 128 per call; lanes = columns
+ * (sources), with p > 64 a lane carries column `lane` and column `lane + 64` (8-byte accesses only).  The matrix is streamed
+ * once per call, whatever p.
+ * One output element is one fp64 add per entry and an exact minimum -- a function of the operands alone: the other columns of
+ * the launch, p, the panel, the leading dimensions and the run do not change a bit of it.  A row without entries copies x to y.
+ * changed: one device int32.  The entry clears it on the stream before the launch; a wave in which any stored element is lower
+ * than the x it replaced stores 1 there (a plain store of the constant from one lane).  Nothing else is shared between
+ * workgroups: no floating-point atomics, no waiting on memory another workgroup writes, no grid barrier; the end of the launch
+ * is the only synchronisation.  The caller repeats rounds (x and y taking turns) until one leaves *changed == 0: that round's
+ * output equals its input.  Round r has every shortest path of at most r edges right, so n_rows rounds always suffice.
+ * y must not overlap x (a round is a pure function of x: the number of rounds is the same every run): a call whose ranges
+ * [x, x + n_rows*ldx) and [y, y + n_rows*ldy) intersect returns -1.  So do, before any launch: a NULL rowptr / x / y / changed; a
+ * NULL col or len for a matrix with rows (one without entries passes any address: they are not read); p out of range; ld < p;
+ * n_rows < 0.  n_rows == 0 launches nothing and still clears *changed.
+ *
+ * meld_edge_lengths_l2: out[e] = sqrt( sum_k (X[i, k] - X[col[e], k])^2 ) for every stored entry e of row i; X [n_rows, ldX]
+ * row-major fp64 in the same row order as the CSR, 1 <= d <= 256, ldX >= d.  The sum is acc = 0; acc = fma(t, t, acc), t =
+ * X[i, k] - X[col[e], k], k ascending: (a - b)^2 == (b - a)^2 exactly and the order is fixed, so the lengths of (i, j) and (j, i)
+ * are bit-equal.  Returns -1 before any launch for a NULL rowptr / X, a NULL col / out for a matrix with rows, d out of range,
+ * ldX < d, n_rows outside [0, 2^31); n_rows == 0 is a successful no-op. */
+int meld_minplus_max_cols(void);
+int meld_minplus_step(const int64_t* rowptr, const int32_t* col, const double* len, int64_t n_rows, const double* x, int64_t ldx,
+                      double* y, int64_t ldy, int p, int32_t* changed, meld_stream_t stream);
+int meld_edge_lengths_l2(const int64_t* rowptr, const int32_t* col, int64_t n_rows, const double* X, int64_t ldX, int d,
+                         double* out, meld_stream_t stream);
+
 /* ---- next#1: normalize_densities (meld/utils.py:35-47) ------------------------------------ */
 /* out[i,:] = in[i,:] / sum_j |in[i,j]|  (rows of zeros are copied unchanged, as sklearn does) */
 int meld_normalize_rows_l1(const double* in, double* out, int64_t n_rows, int p, meld_stream_t stream);

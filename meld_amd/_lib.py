@@ -191,6 +191,9 @@ SIGNATURES = {
     "meld_subgraph_fill": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
     "meld_diffuse_max_cols": (_i32, []),
     "meld_diffuse_step": (_i32, [_ptr, _ptr, _ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _ptr]),
+    "meld_minplus_max_cols": (_i32, []),
+    "meld_minplus_step": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _ptr, _ptr]),
+    "meld_edge_lengths_l2": (_i32, [_ptr, _ptr, _i64, _ptr, _i64, _i32, _ptr, _ptr]),
 }
 
 

@@ -522,6 +522,39 @@ class DeviceGraph:
 
         return diffuse.diffuse(self, F, t=t)
 
+    # -- geodesic distances (meld_amd/geodesic.py, csrc/geodesic.hip): [UPSTREAM graphtools ``BaseGraph.shortest_path``], many
+    # sources per stream of the matrix; scipy's dijkstra bit for bit --------------------------------------------------------------
+    def edge_lengths(self, distance=None):
+        """The lengths the shortest paths add up, as scipy CSR in the caller's cell order with the pattern of ``W`` (a host
+        export, like ``K``): ``"affinity"`` = ``-log W``, ``"data"`` = the euclidean distances of the cells the graph was
+        searched on (exactly symmetric), ``"constant"`` = 1; None: ``"constant"`` for a ``decay=None`` graph, else ``"affinity"``."""
+        from . import geodesic
+
+        return self._scipy(geodesic.edge_lengths_device(self, distance).cpu().numpy())
+
+    def shortest_path_device(self, sources, distance=None, min_only=False, device_order=False, max_rounds=None):
+        """Distances along the graph from each of ``sources`` (integers or a boolean mask; duplicates allowed) as an fp64 device
+        tensor ``[N, p]``, ``+inf`` where there is no path; ``min_only``: ``[N]``, the distance to the nearest source.  Synchronous
+        Bellman-Ford rounds for up to 128 sources per stream of the matrix, until a round lowers nothing: the values are
+        ``scipy.sparse.csgraph.dijkstra(self.edge_lengths(distance), indices=sources)`` bit for bit where all lengths are positive,
+        and a column's values do not depend on the other sources.  Rows and sources in the caller's order unless
+        ``device_order``.  ``geodesic_info`` is ``dict(rounds=[per panel], distance, p)``.  ValueError on a row-sharded graph, for
+        sources out of range and for lengths that are not finite and >= 0 (an adopted graph with weights above 1 under
+        ``"affinity"``); NotImplementedError where ``"data"`` has no cells to measure; RuntimeError after ``max_rounds`` rounds
+        (default ``N``)."""
+        from . import geodesic
+
+        return geodesic.shortest_path_device(self, sources, distance=distance, min_only=min_only, device_order=device_order,
+                                             max_rounds=max_rounds)
+
+    def shortest_path(self, sources=None, distance=None, min_only=False, method="auto"):
+        """``shortest_path_device`` as a host ndarray ``[N, p]``.  ``sources=None``: all cells, offered up to ``FOURIER_MAX_N``
+        cells (the result is dense ``[N, N]``); beyond that ValueError asks for ``sources``.  ``method`` is accepted for
+        graphtools' signature and ignored."""
+        from . import geodesic
+
+        return geodesic.shortest_path(self, sources=sources, distance=distance, min_only=min_only, method=method)
+
     # -- connectivity (meld_amd/components.py, csrc/components.hip): pygsp's ``is_connected`` / ``extract_components`` / ``subgraph``,
     # scipy's labels.  Single-GPU graphs; nothing goes through the host but the counts. ---------------------------------------------
     def connected_components_device(self, recompute=False, max_rounds=None):

@@ -496,6 +496,23 @@ class MELD(GraphEstimator):
         columns = idx if getattr(st, "columns", None) is None else st.columns[idx]
         return pd.DataFrame(values.cpu().numpy(), index=getattr(st, "index", None), columns=columns)
 
+    def geodesic(self, sources, distance=None):
+        """Distances along the fitted graph from the cells ``sources`` (positions: integers or a boolean mask over the cells) to
+        every cell ([UPSTREAM graphtools ``BaseGraph.shortest_path``]): a DataFrame ``[N, len(sources)]`` with the fitted cells'
+        index, its columns labelled by the sources' index labels (their positions where ``fit`` saw no index); ``inf`` where there
+        is no path.  ``distance``: ``"affinity"`` (``-log`` of the weights), ``"data"`` (euclidean distances of the cells the graph
+        was searched on), ``"constant"`` (hops); None: ``"constant"`` for ``decay=None``, else ``"affinity"``.  See
+        ``DeviceGraph.shortest_path_device``."""
+        from . import geodesic
+
+        if self.graph is None:
+            raise ValueError("Estimator must be `fit` before running `geodesic`.")
+        if not hasattr(self.graph, "shortest_path_device"):
+            raise NotImplementedError("the graph of this estimator cannot compute shortest paths")
+        values, idx = geodesic.geodesic(self.graph, sources, distance=distance)
+        index = getattr(getattr(self.graph, "_extend_state", None), "index", None)
+        return pd.DataFrame(values.cpu().numpy(), index=index, columns=idx if index is None else index[idx])
+
     def fit_transform(self, X, sample_labels, **kwargs):
         """Builds the graph on ``X`` and estimates the density of each sample in
         ``sample_labels`` (reference ``meld/meld.py:252-274``)."""
