@@ -120,7 +120,8 @@ def build(force=False, verbose=True):
     hipcc = _hipcc()
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "k16_rows.hpp"), os.path.join(_HERE, "..", "include", "meld_hip.h")]
+    headers = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "k16_rows.hpp"), os.path.join(CSRC, "csr_wave_stream.hpp"),
+               os.path.join(_HERE, "..", "include", "meld_hip.h")]
     procs = []
     objs = []
     for src in SOURCES:

@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from ._graph_steps import require_unsharded, rounds_until_unchanged
 from ._lib import check, get_lib, ptr
 
 __all__ = ["default_max_rounds", "selection_index", "connected_components_device", "subgraph"]
@@ -23,11 +24,6 @@ def default_max_rounds(N):
     if N < 1:
         raise ValueError("a graph has at least one vertex, got N={}".format(N))
     return 4 * (N - 1).bit_length() + 64  # ((N - 1).bit_length() == ceil(log2 N) for N >= 1)
-
-
-def require_unsharded(G, what):
-    if G.n_rows != G.N or getattr(G, "comm", None) is not None:
-        raise ValueError("{} only defined for an unsharded graph".format(what))
 
 
 def selection_index(ind, N):
@@ -88,14 +84,13 @@ def connected_components_device(G, recompute=False, max_rounds=None):
     lib, st = get_lib(), _stream()
     parent = torch.arange(N, dtype=torch.int32, device=dev)
     changed = torch.zeros(1, dtype=torch.int32, device=dev)
-    rounds = 0
-    while True:
-        if rounds >= max_rounds:
-            raise RuntimeError("connected components: no fixed point after {} rounds of hook-and-compress (max_rounds={})".format(rounds, max_rounds))
+    def one_round(_):
         check(lib.meld_cc_round(ptr(G.rowptr), ptr(G.col), N, ptr(parent), ptr(changed), st), "meld_cc_round")
-        rounds += 1
-        if int(changed.item()) == 0:  # (the one device word the host reads per round)
-            break
+
+    def no_fixed_point(r):
+        return "connected components: no fixed point after {} rounds of hook-and-compress (max_rounds={})".format(r, max_rounds)
+
+    rounds = rounds_until_unchanged(one_round, changed, max_rounds, no_fixed_point)
     min_orig = torch.empty(N, dtype=torch.int32, device=dev)
     count = torch.empty(N, dtype=torch.int32, device=dev)
     flags = torch.empty(N, dtype=torch.int32, device=dev)

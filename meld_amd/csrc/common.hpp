@@ -55,6 +55,31 @@ __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// The "lanes = columns" steps over the CSR arrays (csr_wave_stream.hpp): 8 consecutive rows per wave, 4 waves per workgroup, up to
+// 2 columns per lane.
+constexpr int WAVE_STREAM_ROWS = 8;
+constexpr int WAVE_STREAM_MAX_COLS = 128;
+
+// their grid: 32 rows per workgroup, rounded up to a multiple of 8 (the XCD remap of the kernels is then a bijection)
+static inline unsigned wave_stream_grid(int64_t n_rows) { return (unsigned)(ceil_div(ceil_div(n_rows, 4 * WAVE_STREAM_ROWS), 8) * 8); }
+
+// The argument contract of a panel step y = step(x) on row-major blocks with leading dimensions (meld_diffuse_step,
+// meld_minplus_step); `entry` prefixes the message, `required` names the pointers `required_ok` stands for, `values` the array next
+// to col, `pass` what a call is ("step", "round").  MELD_OK, or MELD_ERR_INVALID with the message set: nothing has been launched.
+static inline int check_panel_step(const char* entry, bool required_ok, const char* required, const char* values, const char* pass,
+                                   const void* col, const void* val, int64_t n_rows, const double* x, int64_t ldx, const double* y,
+                                   int64_t ldy, int p) {
+  MELD_CHECK_ARG(required_ok, "%s: %s are required", entry, required);
+  MELD_CHECK_ARG(n_rows >= 0, "%s: n_rows=%lld is negative", entry, (long long)n_rows);
+  MELD_CHECK_ARG(p >= 1 && p <= WAVE_STREAM_MAX_COLS, "%s: p=%d columns (1 <= p <= %d per call)", entry, p, WAVE_STREAM_MAX_COLS);
+  MELD_CHECK_ARG(ldx >= p && ldy >= p, "%s: leading dimensions ldx=%lld, ldy=%lld below p=%d", entry, (long long)ldx, (long long)ldy, p);
+  MELD_CHECK_ARG(n_rows == 0 || (col && val), "%s: col and %s are required for a matrix with rows", entry, values);
+  const uintptr_t x0 = (uintptr_t)x, x1 = x0 + sizeof(double) * (uintptr_t)n_rows * (uintptr_t)ldx;
+  const uintptr_t y0 = (uintptr_t)y, y1 = y0 + sizeof(double) * (uintptr_t)n_rows * (uintptr_t)ldy;
+  MELD_CHECK_ARG(n_rows == 0 || x1 <= y0 || y1 <= x0, "%s: y overlaps x (a %s reads rows of x other rows have written)", entry, pass);
+  return MELD_OK;
+}
+
 // slots of a row bucket of the symmetrisation (assemble.hip; refine.hip's emitting kernel writes into the buckets too)
 constexpr int CSR_BUCKET = 256;
 

@@ -16,7 +16,7 @@
 // lanes per row sum the row's LDS segment and a 2-step shuffle finishes the row.  Rows of any
 // length work: the span is processed in LDS-sized chunks with the row accumulators kept in
 // registers.  HBM-bound: 12 B/nonzero streamed + vector traffic (roofline section).
-#include "common.hpp"
+#include "csr_wave_stream.hpp"
 
 #include <algorithm>
 
@@ -408,112 +408,45 @@ static void launch_cheby(const meld_laplacian_t* L, int ld, int colofs, const do
                      colofs, x_full, x_row_offset, z, y, r, alpha, beta, gamma, coef, dots, chunk, coef_dev);
 }
 
-// Wide signals (the probe block of the filter-bank VertexFrequencyCluster, p = 64 columns): lanes = COLUMNS.  A wave owns a row at
-// a time; for every nonzero the 64 lanes read the 8 p contiguous bytes of the neighbour's row of the iterate (whole cache lines,
-// one request per 128 bytes instead of one per 16) and the matrix is streamed once for all columns -- against p / 2 launches of
-// the two-column kernel, each of which streams it again (3.4 ms per 64-column product at 1M cells).  The row's (value, column)
-// pairs are loaded eight at a time by the first lanes and handed round with v_readlane (scalar address arithmetic, the value as a
-// scalar operand of the FMA); eight gathers in flight per lane.  Rows of a workgroup are consecutive and workgroups are
-// XCD-contiguous, so the rows of the iterate a neighbourhood shares are served by that XCD's L2.
+// Wide signals (the probe block of the filter-bank VertexFrequencyCluster, p = 64 columns): lanes = COLUMNS, the NC = 1 pass of
+// csr_wave_stream.hpp with ldx = ldy = p.  The matrix is streamed once for all columns -- against p / 2 launches of the two-column
+// kernel, each of which streams it again (3.4 ms per 64-column product at 1M cells).
 //     y = alpha (dw .* x - W x) + beta x + gamma z      (y and z may alias: read before write per element)
-constexpr int WIDE_U = 16;    // gathers in flight per lane
-constexpr int WIDE_ROWS = 8;  // rows per wave (consecutive)
+// Gathers index x_full from row 0; x_row_offset applies to the rows' own x only.  The epilogue is left to the compiler's
+// contraction as written (its choice is part of the result's bits).  As compiled: 132 VGPRs, 3 waves per SIMD, no private memory.
+struct ChebyWideOp {
+  const double* __restrict__ dw;
+  const double* __restrict__ x_own;  // x_full at the first local row
+  const double* z;
+  double* y;
+  int p;
+  double alpha, beta, gamma;
+  double dwl;           // lane r: the degree of the wave's row r
+  own_rows<1> xi, zi;   // the rows' own x and z
+  __device__ __forceinline__ void load_rows(const wave_rows<1>& w) {
+    dwl = dw[w.lane_row()];
+    xi.load(x_own, p, w);
+    if (gamma != 0.0)
+      zi.load<true>(z, p, w);
+    else
+      zi.v[0] = 0.0;
+  }
+  static __device__ __forceinline__ double pad() { return 0.0; }
+  static __device__ __forceinline__ double identity() { return 0.0; }
+  static __device__ __forceinline__ double combine(double acc, double v, double xj) { return fma(v, xj, acc); }
+  __device__ __forceinline__ void close_row(int r, int64_t row, const double (&acc)[1], const bool (&on)[1], int lane) {
+    const double xr = xi.v[0][r], zr = zi.v[0][r];
+    if (on[0]) __builtin_nontemporal_store(alpha * (wave_uniform(dwl, r) * xr - acc[0]) + beta * xr + gamma * zr, y + row * p + lane);
+  }
+};
+
 __global__ __launch_bounds__(256) void cheby_step_wide_kernel(const int64_t* __restrict__ rowptr, const int* __restrict__ col,
                                                               const double* __restrict__ val, const double* __restrict__ dw,
                                                               int64_t n_rows, int p, const double* __restrict__ x_full,
                                                               int64_t x_row_offset, const double* z, double* y, double alpha,
                                                               double beta, double gamma) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int nb = gridDim.x;
-  const int per = (nb + 7) >> 3;
-  int64_t rb = (int64_t)(blockIdx.x & 7) * per + (blockIdx.x >> 3);
-  if (rb >= nb) return;
-  const int64_t row_first = (rb * 4 + wv) * WIDE_ROWS;
-  if (row_first >= n_rows) return;  // (uniform)
-  const int n_here = (int)min((int64_t)WIDE_ROWS, n_rows - row_first);
-  const bool on = lane < p;
-  const int lc = on ? lane : 0;
-  // The wave's WIDE_ROWS consecutive rows are ONE stream of entries [E0, E1): the (value, column) pairs are fetched a chunk ahead
-  // of the gathers they feed and the gathers a chunk ahead of the FMAs that consume them, so the two dependent memory latencies
-  // of a chunk overlap with the previous chunk's work and no bubble opens at a row boundary.  Row boundaries, degrees and the
-  // rows' own operands are loaded once, up front (lane r: row r), and handed round with v_readlane.
-  static_assert(WIDE_ROWS + 1 <= 64, "row pointers of a wave are held one per lane");
-  const int64_t rp = rowptr[min(row_first + min(lane, n_here), n_rows)];
-  const double dwl = dw[min(row_first + min(lane, n_here - 1), n_rows - 1)];
-  double xi[WIDE_ROWS], zi[WIDE_ROWS];
-#pragma unroll
-  for (int r = 0; r < WIDE_ROWS; ++r) {
-    const int64_t row = min(row_first + r, n_rows - 1);
-    xi[r] = x_full[(x_row_offset + row) * p + lc];
-    zi[r] = gamma != 0.0 ? __builtin_nontemporal_load(z + row * p + lc) : 0.0;  // (streamed once: leave the L2 to the gathered rows)
-  }
-  auto rp_at = [&](int r) __attribute__((always_inline)) {
-    return (int64_t)(((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(rp >> 32), r) << 32) |
-                     (unsigned)__builtin_amdgcn_readlane((int)rp, r));
-  };
-  const int64_t E0 = rp_at(0), E1 = rp_at(n_here);
-  auto fetch_pairs = [&](int64_t e0, double& vv, int& cc) __attribute__((always_inline)) {
-    const int64_t e = min(e0 + (lane & (WIDE_U - 1)), E1 - 1);
-    vv = (e0 + (lane & (WIDE_U - 1)) < E1) ? __builtin_nontemporal_load(val + max(e, (int64_t)0)) : 0.0;
-    cc = E1 > E0 ? __builtin_nontemporal_load(col + max(e, (int64_t)0)) : 0;
-  };
-  auto gather = [&](int cc, double (&xj)[WIDE_U]) __attribute__((always_inline)) {
-#pragma unroll
-    for (int u = 0; u < WIDE_U; ++u) xj[u] = x_full[(int64_t)__builtin_amdgcn_readlane(cc, u) * p + lc];
-  };
-  int r_cur = 0;
-  int64_t re_cur = rp_at(1);
-  double acc = 0.0;
-  auto flush_rows_until = [&](int64_t e) __attribute__((always_inline)) {  // (uniform) close every row that ends at or before entry e
-    while (r_cur < n_here && e >= re_cur) {
-      // xi / zi of row r_cur: a uniform select over the register array
-      double xr = xi[0], zr = zi[0];
-#pragma unroll
-      for (int r = 1; r < WIDE_ROWS; ++r) {
-        xr = (r == r_cur) ? xi[r] : xr;
-        zr = (r == r_cur) ? zi[r] : zr;
-      }
-      const int dlo = __builtin_amdgcn_readlane(__double2loint(dwl), r_cur), dhi = __builtin_amdgcn_readlane(__double2hiint(dwl), r_cur);
-      if (on) __builtin_nontemporal_store(alpha * (__hiloint2double(dhi, dlo) * xr - acc) + beta * xr + gamma * zr, y + (row_first + r_cur) * p + lane);
-      acc = 0.0;
-      ++r_cur;
-      re_cur = r_cur < n_here ? rp_at(r_cur + 1) : E1 + 1;
-    }
-  };
-  double vA, vB;
-  int cA, cB;
-  double xA[WIDE_U], xB[WIDE_U];
-  fetch_pairs(E0, vA, cA);
-  fetch_pairs(E0 + WIDE_U, vB, cB);
-  gather(cA, xA);
-  for (int64_t e0 = E0; e0 < E1; e0 += 2 * WIDE_U) {
-    // chunk A = [e0, e0 + U), chunk B = [e0 + U, e0 + 2 U); the pairs of the chunk after B and B's gathers go out before A is summed
-    gather(cB, xB);
-    double vN;
-    int cN;
-    fetch_pairs(e0 + 2 * WIDE_U, vN, cN);
-#pragma unroll
-    for (int u = 0; u < WIDE_U; ++u) {
-      flush_rows_until(e0 + u);
-      const int lo = __builtin_amdgcn_readlane(__double2loint(vA), u), hi = __builtin_amdgcn_readlane(__double2hiint(vA), u);
-      acc = fma(__hiloint2double(hi, lo), xA[u], acc);
-    }
-    gather(cN, xA);
-    double vM;
-    int cM;
-    fetch_pairs(e0 + 3 * WIDE_U, vM, cM);
-#pragma unroll
-    for (int u = 0; u < WIDE_U; ++u) {
-      flush_rows_until(e0 + WIDE_U + u);
-      const int lo = __builtin_amdgcn_readlane(__double2loint(vB), u), hi = __builtin_amdgcn_readlane(__double2hiint(vB), u);
-      acc = fma(__hiloint2double(hi, lo), xB[u], acc);
-    }
-    vA = vN;
-    cA = cN;
-    vB = vM;
-    cB = cM;
-  }
-  flush_rows_until(E1 + 1);  // the rows that are left (the last one, and rows without entries)
+  ChebyWideOp op{dw, x_full + x_row_offset * p, z, y, p, alpha, beta, gamma};
+  wave_stream_rows<1>(rowptr, col, val, n_rows, x_full, p, p, op);
 }
 
 // (Round 6, measured and not kept: the same step on PANELS of 16 columns -- four rows per wave, lane = (row group, column), one launch
@@ -536,8 +469,7 @@ extern "C" int meld_cheby_step_wide(const meld_laplacian_t* L, int p, const doub
                  "meld_cheby_step_wide: bad arguments (1 <= p <= 64)");
   MELD_CHECK_ARG(gamma == 0.0 || z != nullptr, "meld_cheby_step_wide: z is required when gamma != 0");
   if (L->n_rows == 0) return MELD_OK;
-  const int64_t nblk = ceil_div(L->n_rows, 4 * WIDE_ROWS);
-  const unsigned grid = (unsigned)(ceil_div(nblk, 8) * 8);
+  const unsigned grid = wave_stream_grid(L->n_rows);
   hipLaunchKernelGGL(cheby_step_wide_kernel, dim3(grid), dim3(256), 0, S(stream), L->rowptr, L->col, L->val, L->dw, L->n_rows, p, x_full,
                      x_row_offset, z, y, alpha, beta, gamma);
   MELD_LAUNCH_CHECK("cheby_step_wide_kernel");

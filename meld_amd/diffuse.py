@@ -16,6 +16,8 @@ import numbers
 
 import numpy as np
 
+from ._graph_steps import csr_operands, is_sharded, require_unsharded
+
 __all__ = ["check_t", "panels", "column_index", "diffuse_device", "impute"]
 
 MAX_COLS = 128  # columns of one launch (``meld_diffuse_max_cols()``; tests/test_diffuse_host.py holds the two together)
@@ -76,11 +78,6 @@ def column_index(genes, n_features, names=None):
 
 
 # -- device side ---------------------------------------------------------------------------------------------------------------
-def _unsharded(G):
-    if G.n_rows != G.N or getattr(G, "comm", None) is not None:
-        raise ValueError("the diffusion operator is only defined for an unsharded graph")
-
-
 def walk_vectors(G):
     """``(kd, s)``: the kernel's diagonal and the row sums ``s = dw + kd`` of ``K`` in the device order, contiguous fp64 device
     tensors, built once and kept on the graph.  ValueError, naming their number, where cells have no positive row sum."""
@@ -127,7 +124,7 @@ def diffuse_device(G, F, t=1, device_order=False):
     from ._lib import check, get_lib, ptr
 
     t = check_t(t)
-    _unsharded(G)
+    require_unsharded(G, "the diffusion operator is")
     X, flat = _signal_device(F, G)
     permuted = G.perm is not None and not device_order
     X = X.index_select(0, G.perm) if (permuted and t > 0) else X.contiguous()
@@ -143,10 +140,7 @@ def diffuse_device(G, F, t=1, device_order=False):
     bufs = (first, second)
     lib = get_lib()
     st = torch.cuda.current_stream().cuda_stream
-    rowptr, col, val = G.rowptr, G.col, G.val
-    if G.nnz == 0:  # (a matrix without entries: any address serves, none is read)
-        col = torch.zeros(1, dtype=torch.int32, device=X.device)
-        val = torch.zeros(1, dtype=torch.float64, device=X.device)
+    rowptr, col, val = csr_operands(G, G.val)
     esz = X.element_size()
     for c0, w in panels(p):  # all t steps of one panel before the next
         src = X
@@ -176,7 +170,7 @@ def diffuse(G, F, t=1):
 def impute_refusal(G):
     """Why ``MELD.impute`` cannot run on this graph (a string), or None."""
     info = getattr(G, "info", None) or {}
-    if G.n_rows != G.N or getattr(G, "comm", None) is not None:
+    if is_sharded(G):
         return "a row-sharded graph cannot impute (every rank holds a slice of the kernel only)"
     st = getattr(G, "_extend_state", None)
     if st is None:

@@ -532,6 +532,16 @@ def _to_device_order(signal, graph):
     return s_dev
 
 
+def device_rows_of(graph, idx):
+    """The device rows of the caller's cells ``idx`` (an int64 device tensor): the inverse of ``graph.perm``."""
+    perm = getattr(graph, "perm", None)
+    if perm is None:
+        return idx
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(perm.shape[0], dtype=perm.dtype, device=perm.device)
+    return inv.index_select(0, idx)
+
+
 def _to_caller_order(r, graph):
     """The local rows [..., rows_pad, p] of a result as [..., N, p] in the caller's row order: all-gather on a shard, cut to
     the N cells, inverse permutation."""

@@ -22,6 +22,7 @@ from __future__ import annotations
 
 import numpy as np
 
+from ._graph_steps import csr_operands, is_sharded, require_unsharded, rounds_until_unchanged
 from .diffuse import panels
 
 __all__ = ["DISTANCES", "check_distance", "default_distance", "check_sources", "data_refusal", "edge_lengths_device",
@@ -72,15 +73,11 @@ def check_sources(sources, N):
     return idx
 
 
-def _sharded(G):
-    return G.n_rows != G.N or getattr(G, "comm", None) is not None
-
-
 def data_refusal(G):
     """Why ``distance="data"`` cannot run on this graph (a string), or None: the lengths are the euclidean distances of the rows
     the graph was searched on, so the graph must keep them and they must be the data."""
     info = getattr(G, "info", None) or {}
-    if _sharded(G):
+    if is_sharded(G):
         return "a row-sharded graph has no data distances (every rank holds a slice of the kernel only)"
     st = getattr(G, "_extend_state", None)
     if st is not None and getattr(st, "metric", None) is not None:
@@ -103,11 +100,6 @@ def data_refusal(G):
 
 
 # -- device side ---------------------------------------------------------------------------------------------------------------
-def _unsharded(G):
-    if _sharded(G):
-        raise ValueError("shortest paths are only defined for an unsharded graph")
-
-
 def edge_lengths_device(G, distance=None):
     """The length of every stored entry: an fp64 device tensor aligned with ``G.col`` (device order), built once per
     ``(graph, distance)`` and kept on the graph.  ``"constant"``: ones.  ``"affinity"``: ``-log(val)``, which needs
@@ -121,7 +113,7 @@ def edge_lengths_device(G, distance=None):
     from ._lib import check, get_lib, ptr
 
     distance = default_distance(G) if distance is None else check_distance(distance)
-    _unsharded(G)
+    require_unsharded(G, "shortest paths are")
     kept = getattr(G, "_edge_lengths", None)
     if kept is None:
         kept = G._edge_lengths = {}
@@ -159,9 +151,10 @@ def shortest_path_device(G, sources, distance=None, min_only=False, device_order
     graph has a long diameter: every round is a launch and a read-back."""
     import torch
 
+    from . import filter as _filter
     from ._lib import check, get_lib, ptr
 
-    _unsharded(G)
+    require_unsharded(G, "shortest paths are")
     N, dev = G.N, G.val.device
     idx = check_sources(sources, N)
     distance = default_distance(G) if distance is None else check_distance(distance)
@@ -174,18 +167,13 @@ def shortest_path_device(G, sources, distance=None, min_only=False, device_order
     info = dict(rounds=[], distance=distance, p=int(idx.shape[0]))
     if p and idx.size:
         rows = torch.from_numpy(idx).to(dev)
-        if G.perm is not None and not device_order:  # caller's cell -> device row
-            inv = torch.empty_like(G.perm)
-            inv[G.perm] = torch.arange(N, dtype=G.perm.dtype, device=dev)
-            rows = inv.index_select(0, rows)
+        if not device_order:
+            rows = _filter.device_rows_of(G, rows)
         D[rows, 0 if min_only else torch.arange(p, device=dev)] = 0.0
     if p and N:
         lib = get_lib()
         st = torch.cuda.current_stream().cuda_stream
-        col = G.col
-        if G.nnz == 0:  # (a matrix without entries: any address serves, none is read)
-            col = torch.zeros(1, dtype=torch.int32, device=dev)
-            L = torch.zeros(1, dtype=torch.float64, device=dev)
+        rowptr, col, L = csr_operands(G, L)
         # the rounds of a panel take turns between its columns of D and of `other`, a block of the same shape (the same columns of
         # both: the ranges the entry compares never meet); the round that lowers nothing leaves both equal, so D holds the result
         # whichever it wrote
@@ -193,22 +181,18 @@ def shortest_path_device(G, sources, distance=None, min_only=False, device_order
         changed = torch.zeros(1, dtype=torch.int32, device=dev)
         esz = D.element_size()
         for c0, w in panels(p):  # all rounds of one panel before the next
-            bufs = ((D.data_ptr() + c0 * esz, p), (other.data_ptr() + c0 * esz, p))
-            rounds = 0
-            while True:
-                if rounds >= max_rounds:
-                    raise RuntimeError("shortest paths: no fixed point after {} rounds (max_rounds={}) for sources {} .. {}".format(
-                        rounds, max_rounds, c0, c0 + w - 1))
-                (x, ldx), (y, ldy) = bufs[rounds & 1], bufs[(rounds + 1) & 1]
-                check(lib.meld_minplus_step(ptr(G.rowptr), ptr(col), ptr(L), N, x, ldx, y, ldy, w, ptr(changed), st), "meld_minplus_step")
-                rounds += 1
-                if int(changed.item()) == 0:  # (the one device word the host reads per round)
-                    break
-            info["rounds"].append(rounds)
+            bufs = (D.data_ptr() + c0 * esz, other.data_ptr() + c0 * esz)
+
+            def one_round(r):
+                check(lib.meld_minplus_step(ptr(rowptr), ptr(col), ptr(L), N, bufs[r & 1], p, bufs[(r + 1) & 1], p, w, ptr(changed), st),
+                      "meld_minplus_step")
+
+            def no_fixed_point(r):
+                return "shortest paths: no fixed point after {} rounds (max_rounds={}) for sources {} .. {}".format(r, max_rounds, c0, c0 + w - 1)
+
+            info["rounds"].append(rounds_until_unchanged(one_round, changed, max_rounds, no_fixed_point))
     G.geodesic_info = info
     if G.perm is not None and not device_order:
-        from . import filter as _filter
-
         D = _filter._to_caller_order(D, G) if p else D
     return D[:, 0] if min_only else D
 

@@ -145,7 +145,9 @@ def test_edge_length_entry_rejects_its_contract_before_any_launch():
 
 
 def test_round_kernels_compile_without_private_memory():
-    """Both instantiations at the diffusion kernel's chunk sizes: no private memory, 4 and 3 waves per SIMD."""
+    """Both instantiations at the diffusion kernel's chunk sizes: no private memory, 4 and 3 waves per SIMD.  The
+    round shares its pass over the matrix (csrc/csr_wave_stream.hpp) with the diffusion step and the wide recurrence step: the
+    same holds for all five kernels, the wide step (which also keeps a z row) at 3 waves per SIMD."""
     import os
 
     from meld_amd import build as mbuild
@@ -160,6 +162,15 @@ def test_round_kernels_compile_without_private_memory():
     one, two = (rows[k] for k in step)  # (mangled names: ...ILi1EE..., ...ILi2EE...)
     assert "ILi1E" in step[0] and "ILi2E" in step[1]
     assert one["Occupancy [waves/SIMD]:"] >= 4 and two["Occupancy [waves/SIMD]:"] >= 3, (one, two)
+
+    for src, kernel, waves in (("diffuse.hip", "diffuse_step_kernel", (4, 3)), ("spmm.hip", "cheby_step_wide_kernel", (3,))):
+        assert src in mbuild.SOURCES
+        rows = _resource_usage(os.path.join(ROOT, "meld_amd", "csrc", src))
+        names = sorted(k for k in rows if kernel in k)
+        assert len(names) == len(waves), sorted(rows)
+        for name, least in zip(names, waves):  # (sorted: ...ILi1EE... before ...ILi2EE...)
+            print(name, rows[name])
+            assert rows[name]["ScratchSize [bytes/lane]:"] == 0 and rows[name]["Occupancy [waves/SIMD]:"] >= least, (name, rows[name])
 
 
 # -- the rounds on the host ---------------------------------------------------------------------------------------------------------
