@@ -1278,8 +1278,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
 
 // Final form of the candidate rows: one wave per row sorts its entries by (value, index) with a bitonic network on
 // 64-bit keys (ordered value bits : index; element i = 64 e + lane, so exchanges at distance >= 64 stay inside a
-// lane and the others are one __shfl_xor), keeps the ksel smallest, converts them to input units
-// ((v + |q|^2) / s^2) and writes the row's length.  cnt: in = half-row lengths n0 | n1 << 16, out = min(n, ksel).
+// lane and the others are one __shfl_xor) -- the value being the entry in input units, (v + |q|^2) / s^2, so that the row
+// leaves sorted by (d2, index) as stored -- keeps the ksel smallest and writes the row's length.  cnt: in = half-row lengths n0 | n1 << 16, out = min(n, ksel).
 // 1M rows of <= 128 entries: 0.8 ms (the in-kernel ranking it replaces: 4.8 ms).
 // (k16_bitonic_sort: k16_rows.hpp)
 // (the network is as small as the row allows: most rows hold fewer than 128 entries, many fewer than 64)
@@ -1292,14 +1292,16 @@ __device__ __forceinline__ void k16_finish_row(float* __restrict__ drow, int* __
     const int i = lane + 64 * e;                        // i-th entry of the packed row: first half-row, then second
     const int p = i < n0 ? i : half + (i - n0);
     key[e] = ~0ull;
-    if (i < n_all) key[e] = ((unsigned long long)ordered_bits(drow[p] + 0.0f) << 32) | (unsigned)irow[p];  // (+0: -0 and +0 tie)
+    // (the key is the value the row leaves with: two raw values that round to one d2 are ranked by index, as the contract says --
+    // sorted on the raw value they left in raw order, a row of equal d2 with its indices out of order)
+    if (i < n_all) key[e] = ((unsigned long long)ordered_bits((drow[p] + add) * out_scale + 0.0f) << 32) | (unsigned)irow[p];  // (+0: -0 and +0 tie)
   }
   k16_bitonic_sort<SL>(key, lane);
 #pragma unroll
   for (int e = 0; e < SL; ++e) {
     const int i = 64 * e + lane;
     if (i < n) {
-      drow[i] = (from_ordered_bits((unsigned)(key[e] >> 32)) + add) * out_scale;
+      drow[i] = from_ordered_bits((unsigned)(key[e] >> 32));
       irow[i] = (int)(unsigned)key[e];
     }
   }

@@ -86,18 +86,18 @@ __device__ __forceinline__ double decay_kernel(double dist, double bw, double de
 // CUs, TCP busy (TCP_GATE_EN1) 96 % of the time, L2 hit rate 85 %, 2.5-5 GB from the fabric for 18.7 GB gathered
 // (profiles/r06_refine_pmc.txt).  The query row sits in LDS; the four lanes' partial sums meet by two DPP exchanges.
 // A raw candidate row of the split-fp16 search (two half-rows of n0 and n_all - n0 unsorted entries) ranked in registers exactly as
-// knn16_finish_rows_kernel ranks it: 64-bit keys (ordered bits of v + 0 : index), the smallest network that holds the row; out[e] =
+// knn16_finish_rows_kernel ranks it: 64-bit keys (ordered bits of (v + add) * out_scale + 0 : index), the smallest network that holds the row; out[e] =
 // the key of rank 64 e + lane (e < 2: at most 128 entries are kept), ~0 behind the row's end.
 template <int SL>
-__device__ __forceinline__ void rf_rank_raw_row(const float* drow, const int* irow, int n0, int half, int n_all, int lane,
-                                                unsigned long long (&out)[2]) {
+__device__ __forceinline__ void rf_rank_raw_row(const float* drow, const int* irow, int n0, int half, int n_all, int lane, float add,
+                                                float out_scale, unsigned long long (&out)[2]) {
   unsigned long long key[SL];
 #pragma unroll
   for (int e = 0; e < SL; ++e) {
     const int i = lane + 64 * e;
     const int p = i < n0 ? i : half + (i - n0);
     key[e] = ~0ull;
-    if (i < n_all) key[e] = ((unsigned long long)ordered_bits(drow[p] + 0.0f) << 32) | (unsigned)irow[p];  // (+0: -0 and +0 tie)
+    if (i < n_all) key[e] = ((unsigned long long)ordered_bits((drow[p] + add) * out_scale + 0.0f) << 32) | (unsigned)irow[p];  // (+0: -0 and +0 tie)
   }
   k16_bitonic_sort<SL>(key, lane);
   out[0] = key[0];
@@ -145,15 +145,15 @@ __global__ __launch_bounds__(256) void refine_kernel(
     unsigned long long key[2];
     // (every load of the row happens before its first store: all lanes of the wave pass the sort's shuffles in between)
     if (n_all <= 64)
-      rf_rank_raw_row<1>(raw_d2 + ro, raw_idx + ro, n0, cap >> 1, n_all, lane, key);
+      rf_rank_raw_row<1>(raw_d2 + ro, raw_idx + ro, n0, cap >> 1, n_all, lane, add, out_scale, key);
     else if (n_all <= 128)
-      rf_rank_raw_row<2>(raw_d2 + ro, raw_idx + ro, n0, cap >> 1, n_all, lane, key);
+      rf_rank_raw_row<2>(raw_d2 + ro, raw_idx + ro, n0, cap >> 1, n_all, lane, add, out_scale, key);
     else
-      rf_rank_raw_row<K16_ROW_SLOTS>(raw_d2 + ro, raw_idx + ro, n0, cap >> 1, n_all, lane, key);
+      rf_rank_raw_row<K16_ROW_SLOTS>(raw_d2 + ro, raw_idx + ro, n0, cap >> 1, n_all, lane, add, out_scale, key);
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       idx_raw[e] = (int)(unsigned)key[e];
-      d2_raw[e] = (from_ordered_bits((unsigned)(key[e] >> 32)) + add) * out_scale;
+      d2_raw[e] = from_ordered_bits((unsigned)(key[e] >> 32));
     }
     const float k_lo = __shfl(d2_raw[0], knn & 63, 64), k_hi = __shfl(d2_raw[1], knn & 63, 64);
     d2_knn = knn < 64 ? k_lo : k_hi;  // (used where n > knn only)
