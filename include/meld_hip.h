@@ -899,6 +899,48 @@ int meld_minplus_step(const int64_t* rowptr, const int32_t* col, const double* l
 int meld_edge_lengths_l2(const int64_t* rowptr, const int32_t* col, int64_t n_rows, const double* X, int64_t ldX, int d,
                          double* out, meld_stream_t stream);
 
+/* ---- landmark operator (csrc/landmark.hip; replaces [UPSTREAM graphtools 1.5.x LandmarkGraph.build_landmark_op,
+ *      _landmarks_to_data and LandmarkGraph.extend_to_data, unpinned: not importable next to this code], which the reference reaches
+ *      by forwarding n_landmark at meld/meld.py:105,118) -------------------------------------------------------------------------
+ * Everything is fp64; no atomics; no workgroup waits on memory another writes; every output is a function of the operands alone,
+ * the same bits every run.  meld_landmark_max() = 4096 is the largest number of landmarks L (the Gram's LDS accumulator: 32 KB).
+ *
+ * Merge by label: B = M C for a CSR matrix M [n_rows, n_cols] and the one-hot C [n_cols, L] of label[] -- graphtools' per-cluster
+ * sums of the kernel's columns (``pmn`` before its normalisation, by the kernel's symmetry), and for the kernel rows of new cells
+ * the sums extend_to_data normalises.  Two launches with a scan of the caller's in between:
+ * meld_landmark_merge_count: counts[i] (int32 [n_rows]) = the number of distinct labels in row i, and marked[] (int32 scratch:
+ *   one element per stored entry, plus one per row with has_diag; row i starts at rowptr[i] + (has_diag ? i : 0)) = every entry's
+ *   label, the sign bit set where an earlier entry of the row carries the same label.  rowptr[n_rows + 1] int64, col[nnz] int32 in
+ *   [0, n_cols); label[n_cols] int32 in [0, L) (the caller's to check: labels are stored, never used as addresses); colmap NULL or
+ *   int64 [n_cols]: label[colmap[c]] is the label of column c (a graph in its device order with labels in the caller's order:
+ *   colmap = perm).  has_diag != 0 (square matrices only) adds the entry (i, label of column i) behind the stored entries of row i.
+ * meld_landmark_merge_fill: with out_rowptr[n_rows + 1] = the exclusive scan of counts (meld_exclusive_scan_i32_i64), writes the
+ *   CSR [n_rows, L]: out_col / out_val [out_rowptr[n_rows]] hold every label present in the row once, ascending; a value is the sum
+ *   of the merged entries in storage order, the diagonal kd[i] (kd NULL: none; it must be given exactly where has_diag was) last.
+ *   rowsum[i] = all values of row i in storage order, the diagonal last.  A row without entries and without a diagonal is empty,
+ *   its rowsum 0.  Rows may have any length (the work is quadratic in it: every entry is compared with every other, in LDS tiles
+ *   of 256).
+ *
+ * meld_landmark_gram: op[L, L] row-major = diag(1 / s) A^T diag(1 / r) A and s[L] = the column sums of A, for A [n_cells, L] as the
+ *   merged CSR above (labels distinct and ascending inside a row) and its transpose t_* [L, n_cells] with the cells ascending inside
+ *   a landmark (meld_csr_transpose_keys + meld_sort_pairs_u64_f64 + meld_csr_from_keys), r[n_cells] the row sums.  One workgroup
+ *   per landmark l: acc[m] = fma(A[j, l] / r[j], A[j, m], acc[m]) over the cells j of the landmark in ascending order (r[j] <= 0
+ *   contributes nothing), op[l, m] = acc[m] / s[l] (one true division; a row with s[l] <= 0 is zeros); s[l] adds the entries
+ *   e, e + 64, ... of row l of the transpose per lane, then the 64 lanes by a xor butterfly.
+ *
+ * Each entry returns -1 before any launch for a NULL required pointer (a matrix without rows passes any address for its columns
+ * and values), n_landmark outside [1, meld_landmark_max()], sizes outside [0, 2^31), has_diag on a matrix that is not square.
+ * n_rows == 0 is a successful no-op; meld_landmark_gram with n_cells == 0 stores zeros. */
+int meld_landmark_max(void);
+int meld_landmark_merge_count(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_cols, const int32_t* label,
+                              int n_landmark, const int64_t* colmap, int has_diag, int32_t* marked, int32_t* counts,
+                              meld_stream_t stream);
+int meld_landmark_merge_fill(const int64_t* rowptr, const double* val, const double* kd, int64_t n_rows, const int32_t* marked,
+                             const int64_t* out_rowptr, int32_t* out_col, double* out_val, double* rowsum, meld_stream_t stream);
+int meld_landmark_gram(const int64_t* a_rowptr, const int32_t* a_col, const double* a_val, int64_t n_cells, const int64_t* t_rowptr,
+                       const int32_t* t_col, const double* t_val, int n_landmark, const double* r, double* op, double* s,
+                       meld_stream_t stream);
+
 /* ---- next#1: normalize_densities (meld/utils.py:35-47) ------------------------------------ */
 /* out[i,:] = in[i,:] / sum_j |in[i,j]|  (rows of zeros are copied unchanged, as sklearn does) */
 int meld_normalize_rows_l1(const double* in, double* out, int64_t n_rows, int p, meld_stream_t stream);

@@ -194,6 +194,10 @@ SIGNATURES = {
     "meld_minplus_max_cols": (_i32, []),
     "meld_minplus_step": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _i64, _ptr, _i64, _i32, _ptr, _ptr]),
     "meld_edge_lengths_l2": (_i32, [_ptr, _ptr, _i64, _ptr, _i64, _i32, _ptr, _ptr]),
+    "meld_landmark_max": (_i32, []),
+    "meld_landmark_merge_count": (_i32, [_ptr, _ptr, _i64, _i64, _ptr, _i32, _ptr, _i32, _ptr, _ptr, _ptr]),
+    "meld_landmark_merge_fill": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "meld_landmark_gram": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _ptr]),
 }
 
 

@@ -112,11 +112,11 @@ def _lloyd_step_library(Y, C, lab):
     return newC, inertia
 
 
-def _kmeans(Y, k, n_init=10, max_iter=300, tol=1e-4, seed=None):
+def _kmeans(Y, k, n_init=10, max_iter=300, tol=1e-4, seed=None, info=None):
     """Seeded k-means++ initialisation + Lloyd iterations on the device; best inertia of ``n_init``
     runs (sklearn's ``KMeans`` defaults; its relative tolerance is on the centre shift).  The Lloyd step is
     the HIP kernel of ``csrc/kmeans.hip`` for d <= 32, k <= 64 (what PCA(n_clusters) hands over for up to 32 clusters),
-    library kernels beyond."""
+    library kernels beyond.  ``info``: a dict that receives ``iterations`` (Lloyd steps of the run kept) and ``inertia``."""
     from ._lib import get_lib
 
     Y = Y.contiguous()
@@ -155,10 +155,13 @@ def _kmeans(Y, k, n_init=10, max_iter=300, tol=1e-4, seed=None):
             C = newC.contiguous()
             if (_it & 7) == 7 and float(shift) <= var_tol:  # one host sync per 8 iterations
                 break
+        steps = _it + 1 if max_iter > 0 else 0
         _, inertia = _lloyd_step(Y, C, lab, scratch) if scratch is not None else _lloyd_step_library(Y, C, lab)
         inertia = float(inertia)
         if best is None or inertia < best[0]:
-            best = (inertia, lab.to(torch.int64).clone())
+            best = (inertia, lab.to(torch.int64).clone(), steps)
+    if info is not None:
+        info.update(iterations=best[2], inertia=best[0])
     return best[1]
 
 

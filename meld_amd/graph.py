@@ -438,6 +438,24 @@ class DeviceGraph:
         raise NotImplementedError("the landmark operator (graphtools LandmarkGraph.landmark_op) is not implemented; "
                                   "MELD's density estimate does not use it")
 
+    def landmarks(self, n_landmark=None, clusters=None, n_svd=100, random_state=None, recompute=False):
+        """graphtools' ``LandmarkGraph`` for this graph as a ``landmark.Landmarks`` record (``meld_amd/landmark.py``,
+        ``csrc/landmark.hip``): ``clusters`` / ``clusters_device``, ``transitions`` (``[N, L]``) / ``transitions_device``,
+        ``landmark_op`` (``[L, L]``) / ``landmark_op_device``, ``landmark_sums``, ``extend_to_data(Y)`` and ``interpolate(T, Y=None)``
+        with their ``_device`` forms.  The record is built on the device and kept per argument set (``recompute`` builds it anew).
+
+        ``clusters``: one integer per cell in the caller's order (host or device), compacted to the labels present (landmark ``l``
+        is the ``l``-th smallest label); otherwise the cells are clustered into at most ``n_landmark`` landmarks (default: the
+        ``n_landmark`` the graph was fitted with) by k-means on ``diff_op @ V``, ``V`` the leading ``min(n_svd, n_landmark)`` singular
+        vectors of the symmetric diffusion affinity from a seeded randomized range finder -- the same ``random_state`` gives the same labels.
+        ValueError without ``n_landmark`` and ``clusters``, for ``n_landmark >= N`` or above ``landmark.LANDMARK_MAX``, for bad
+        ``clusters`` (TypeError for a dtype that is not integer) and on a row-sharded graph.  The ``landmark_op`` property of the
+        graph itself stays unimplemented: the operator lives on the record."""
+        from . import landmark
+
+        return landmark.landmarks(self, n_landmark=n_landmark, clusters=clusters, n_svd=n_svd, random_state=random_state,
+                                  recompute=recompute)
+
     def kernel_diagonal(self):
         """Diagonal of the kernel matrix K in the device order: K_ii = 1 / (ksum_i^2)^anisotropy for a
         graph built here (the alpha-decay kernel has 1 on its diagonal before the anisotropy

@@ -59,7 +59,8 @@ class MELD(GraphEstimator):
     lap_type : {'combinatorial', 'normalized'}, default 'combinatorial' (validated and stored;
         like the reference it is never forwarded, the Laplacian is always combinatorial)
     sample_normalize : bool, default True -- indicator columns are scaled to sum to 1
-    anisotropy : default 1;  n_landmark : default None (accepted; the filter never uses graphtools' landmark operator)
+    anisotropy : default 1;  n_landmark : default None (recorded; the filter never uses graphtools' landmark operator,
+        ``landmarks()`` builds it with that many landmarks)
     **kwargs : graph parameters -- knn=5, decay=40, n_pca=100, thresh=1e-4,
         distance='euclidean', n_jobs, random_state, verbose; ``ksel`` (candidate list length of the
         GPU search) and ``lmax`` are extensions: a number injects the Laplacian's spectral bound,
@@ -209,7 +210,7 @@ class MELD(GraphEstimator):
         G.bandwidth_to_metric = bw_to_metric
         # n_landmark (reference meld/meld.py:105,118 forwards it to graphtools): a graphtools LandmarkGraph has the same kernel,
         # weights and Laplacian as the plain graph -- the landmark operator is a lazily built extra that MELD's filter never
-        # touches -- so the parameter is accepted and recorded; asking the graph for the operator itself is what is not implemented
+        # touches -- so the parameter is recorded here and the operator is built on request (``landmarks()``, meld_amd/landmark.py)
         G.n_landmark = self.n_landmark
         if plan.keeps_cells:
             # what new cells need (meld_amd/extend.py): the matrix the search saw, in the caller's order (a reference: the graph
@@ -512,6 +513,15 @@ class MELD(GraphEstimator):
         values, idx = geodesic.geodesic(self.graph, sources, distance=distance)
         index = getattr(getattr(self.graph, "_extend_state", None), "index", None)
         return pd.DataFrame(values.cpu().numpy(), index=index, columns=idx if index is None else index[idx])
+
+    def landmarks(self, **kwargs):
+        """The landmark record of the fitted graph ([UPSTREAM graphtools ``LandmarkGraph``], what ``n_landmark`` yields there):
+        ``DeviceGraph.landmarks(**kwargs)`` -- ``n_landmark`` defaults to the estimator's, ``clusters`` passes labels in."""
+        if self.graph is None:
+            raise ValueError("Estimator must be `fit` before running `landmarks`.")
+        if not hasattr(self.graph, "landmarks"):
+            raise NotImplementedError("the graph of this estimator cannot build landmarks")
+        return self.graph.landmarks(**kwargs)
 
     def fit_transform(self, X, sample_labels, **kwargs):
         """Builds the graph on ``X`` and estimates the density of each sample in
