@@ -941,6 +941,28 @@ int meld_landmark_gram(const int64_t* a_rowptr, const int32_t* a_col, const doub
                        const int32_t* t_col, const double* t_val, int n_landmark, const double* r, double* op, double* s,
                        meld_stream_t stream);
 
+/* ---- metric MDS of the PHATE embedding (csrc/mds.hip; replaces the metric stage of [UPSTREAM phate 1.0.x phate.mds.embed_MDS,
+ *      unpinned: not importable next to this code], which every notebook of the reference and Benchmarker.fit_phate
+ *      (meld/benchmark.py) reach through phate.PHATE) -----------------------------------------------------------------------------
+ * Everything is fp64; one launch per step; no atomics; no workgroup waits on memory another writes; every output is a function of
+ * the operands alone, the same bits every run.  meld_smacof_max_dim() = 8 is the largest number of embedding dimensions.
+ *
+ * meld_smacof_step: one SMACOF step (the Guttman transform with unit weights) from the configuration Z [n, dim] towards the target
+ *   distances D [n, n] (row-major, leading dimension ldD >= n; row i reads D[i, 0:n] only, D need not be symmetric), and the
+ *   stress terms of Z itself.  With d_ij = |Z[i] - Z[j]|_2 from direct differences (fma chain over the components, one sqrt):
+ *     Z_out[i]      = (1 / n) sum_{j != i, d_ij > 0} (D[i, j] / d_ij) (Z[i] - Z[j])
+ *     row_stress[i] = sum_{j != i} (d_ij - D[i, j])^2          (a pair with d_ij == 0 contributes D[i, j]^2 here, nothing above)
+ *   so that stress(Z) = 1/2 sum_i row_stress[i] (the caller's sum).  Z and Z_out [n, dim] row-major, distinct buffers (the caller
+ *   ping-pongs them); row_stress [n].  Order of the sums: lane l of a wave adds the columns l, l + 64, l + 128, ... in ascending
+ *   order, then the 64 lanes by a xor butterfly; one true division by n.  A workgroup takes 8 consecutive rows and stages Z in LDS
+ *   in tiles of 256 points its rows share; D is read once.
+ *
+ * Returns -1 before any launch for a NULL pointer, dim outside [1, meld_smacof_max_dim()], ldD < n, n < 0 and Z == Z_out.  n == 0
+ * is a successful no-op; n == 1 stores zeros. */
+int meld_smacof_max_dim(void);
+int meld_smacof_step(const double* D, int64_t ldD, int n, int dim, const double* Z, double* Z_out, double* row_stress,
+                     meld_stream_t stream);
+
 /* ---- next#1: normalize_densities (meld/utils.py:35-47) ------------------------------------ */
 /* out[i,:] = in[i,:] / sum_j |in[i,j]|  (rows of zeros are copied unchanged, as sklearn does) */
 int meld_normalize_rows_l1(const double* in, double* out, int64_t n_rows, int p, meld_stream_t stream);

@@ -198,6 +198,8 @@ SIGNATURES = {
     "meld_landmark_merge_count": (_i32, [_ptr, _ptr, _i64, _i64, _ptr, _i32, _ptr, _i32, _ptr, _ptr, _ptr]),
     "meld_landmark_merge_fill": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
     "meld_landmark_gram": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _ptr]),
+    "meld_smacof_max_dim": (_i32, []),
+    "meld_smacof_step": (_i32, [_ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr, _ptr]),
 }
 
 

@@ -15,6 +15,11 @@ import numpy as np
 __all__ = ["Benchmarker"]
 
 
+# the graph keywords ``fit_graph`` hands to the device builder (graphtools' names)
+_GRAPH_KEYWORDS = {"knn", "decay", "thresh", "ksel", "sample_idx", "n_landmark", "verbose", "distance", "n_jobs", "lmax", "bandwidth",
+                   "bandwidth_scale", "knn_max", "kernel_symm", "theta", "anisotropy"}
+
+
 def _standardise(coords):
     """Column-wise z-scores unless the embedding is already centred (the reference's rule)."""
     coords = np.asarray(coords)
@@ -64,9 +69,7 @@ class Benchmarker(object):
         # graphtools accepts more graph keywords than the device builder implements: those are rejected here, by name,
         # instead of being stored and silently ignored (the graph would differ from the reference's for the same call)
         # (n_jobs and lmax do not change the graph: MELD / GraphEstimator take them, graphtools ran fit_graph(data, n_jobs=-1))
-        known = {"knn", "decay", "thresh", "ksel", "sample_idx", "n_landmark", "verbose", "distance", "n_jobs", "lmax",
-                 "bandwidth", "bandwidth_scale", "knn_max", "kernel_symm", "theta"}
-        unknown = sorted(k for k in kwargs if k not in known | {"anisotropy"})
+        unknown = sorted(k for k in kwargs if k not in _GRAPH_KEYWORDS)
         if unknown:
             raise NotImplementedError("graph options {} are not implemented by the MI355X graph builder".format(unknown))
         seed = self.seed
@@ -78,10 +81,23 @@ class Benchmarker(object):
         return self.graph
 
     def fit_phate(self, data, **kwargs):
-        """3-d PHATE embedding of ``data`` (needs the optional ``phate`` package, as in the reference)."""
-        import phate
+        """3-d PHATE embedding of ``data``: the ``phate`` package where it imports (as in the reference), else the device embedding
+        of ``meld_amd/phate.py`` on a graph built with PHATE's defaults (``n_pca=100``, ``knn=5``, ``decay=40``, no anisotropy, the
+        seed as ``random_state``) -- keywords that are graph keywords go to the graph, the rest to ``graph.phate``."""
+        try:
+            import phate
+        except ImportError:
+            phate = None
+        if phate is not None:
+            self.set_phate(phate.PHATE(n_components=3, **kwargs).fit_transform(data))
+            return self.data_phate
+        from .meld import MELD
 
-        self.set_phate(phate.PHATE(n_components=3, **kwargs).fit_transform(data))
+        graph_kwargs = dict(n_pca=100, knn=5, decay=40, anisotropy=0, verbose=False)
+        graph_kwargs.update({k: kwargs.pop(k) for k in list(kwargs) if k in _GRAPH_KEYWORDS or k == "n_pca"})
+        kwargs.pop("n_components", None)  # (always three: the ground truth is drawn over three coordinates)
+        graph = MELD(random_state=self.seed, **graph_kwargs).fit(data).graph
+        self.set_phate(graph.phate(n_components=3, **kwargs).embedding)
         return self.data_phate
 
     def generate_ground_truth_pdf(self, data_phate=None):

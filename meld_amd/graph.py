@@ -456,6 +456,28 @@ class DeviceGraph:
         return landmark.landmarks(self, n_landmark=n_landmark, clusters=clusters, n_svd=n_svd, random_state=random_state,
                                   recompute=recompute)
 
+    def phate(self, n_components=2, t="auto", gamma=1, n_landmark=None, clusters=None, n_svd=100, mds="metric", max_iter=3000,
+              eps=1e-6, t_max=100, random_state=None, recompute=False):
+        """The PHATE embedding of this graph as a ``phate.PhateEmbedding`` record (``meld_amd/phate.py``, ``csrc/mds.hip``; [UPSTREAM
+        phate ``PHATE.fit_transform``, unpinned: every stage is defined in ``meld_amd/phate.py``]): ``embedding`` (``[N,
+        n_components]``, the caller's cell order) / ``embedding_device``, ``landmark_embedding``, ``t``, ``entropy``,
+        ``potential_device``, ``distances_device``, ``stress``, ``normalized_stress``, ``iterations``, ``landmarks``, ``info``, and
+        ``transform(Y)`` / ``transform_device(Y)`` for new cells.  Built on the device and kept per argument set (``recompute``
+        builds it anew).
+
+        The operator is ``landmarks(n_landmark, clusters=, n_svd=, random_state=).landmark_op_device`` (``n_landmark``: the graph's
+        own, else 2000); a graph of at most ``n_landmark`` cells without ``clusters`` embeds its dense ``diff_op`` directly.  ``t``: a
+        positive integer or ``"auto"`` (the knee of the von Neumann entropy of the operator's powers 1 .. ``t_max``); ``gamma`` in
+        ``[-1, 1]`` selects the potential (1: ``-log``); ``mds``: ``"metric"`` (classical MDS, then SMACOF for at most ``max_iter``
+        steps, to a relative stress decrease of ``eps``) or ``"classic"``.  ValueError, with the value, for ``n_components`` outside
+        ``1 .. 8`` or not below the operator's rows, a ``t`` that is no positive integer, ``gamma`` outside ``[-1, 1]``, ``t_max <
+        3``, an unknown ``mds``, and on a row-sharded graph; the refusals of ``landmarks()`` and of the extension to new cells
+        pass through."""
+        from . import phate
+
+        return phate.phate(self, n_components=n_components, t=t, gamma=gamma, n_landmark=n_landmark, clusters=clusters, n_svd=n_svd,
+                           mds=mds, max_iter=max_iter, eps=eps, t_max=t_max, random_state=random_state, recompute=recompute)
+
     def kernel_diagonal(self):
         """Diagonal of the kernel matrix K in the device order: K_ii = 1 / (ksum_i^2)^anisotropy for a
         graph built here (the alpha-decay kernel has 1 on its diagonal before the anisotropy

@@ -523,6 +523,19 @@ class MELD(GraphEstimator):
             raise NotImplementedError("the graph of this estimator cannot build landmarks")
         return self.graph.landmarks(**kwargs)
 
+    def phate(self, **kwargs):
+        """The PHATE embedding of the fitted cells ([UPSTREAM phate ``PHATE.fit_transform``], what the reference's notebooks plot
+        the densities over): ``DeviceGraph.phate(**kwargs).embedding`` as a DataFrame ``[N, n_components]`` with the fitted cells'
+        index and the columns ``PHATE1``, ``PHATE2``, ...; the record itself (stress, ``t``, ``transform`` for new cells) is
+        ``op.graph.phate(**kwargs)``, kept on the graph."""
+        if self.graph is None:
+            raise ValueError("Estimator must be `fit` before running `phate`.")
+        if not hasattr(self.graph, "phate"):
+            raise NotImplementedError("the graph of this estimator cannot build a PHATE embedding")
+        coords = self.graph.phate(**kwargs).embedding
+        index = getattr(getattr(self.graph, "_extend_state", None), "index", None)
+        return pd.DataFrame(coords, index=index, columns=["PHATE{}".format(c + 1) for c in range(coords.shape[1])])
+
     def fit_transform(self, X, sample_labels, **kwargs):
         """Builds the graph on ``X`` and estimates the density of each sample in
         ``sample_labels`` (reference ``meld/meld.py:252-274``)."""
