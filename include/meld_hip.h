@@ -963,6 +963,51 @@ int meld_smacof_max_dim(void);
 int meld_smacof_step(const double* D, int64_t ldD, int n, int dim, const double* Z, double* Z_out, double* row_stress,
                      meld_stream_t stream);
 
+/* ---- Louvain communities of a CSR graph (csrc/louvain.hip; the reference clusters its cells with scanpy's louvain in
+ *      comparison/comparison.py, find_n_clusters) --------------------------------------------------------------------------------
+ * The graph: rowptr[n + 1] int64, col[nnz] int32 in [0, n), val[nnz] fp64 >= 0, symmetric; an entry (i, i) is the diagonal A_ii.
+ * k = A 1, two_m = 1^T A 1.  Labels are int32 in [0, n): community ids are vertex numbers.  Everything is fp64, there are no
+ * floating-point atomics, every output is a function of the operands alone.
+ *
+ * meld_louvain_move: one synchronous round.  For vertex i in community a = label[i], with w_b = the entries A_ij, j != i, of the row
+ *   whose column carries label b, added in storage order, and g(b) = w_b two_m - (gamma k[i]) (tot[b] - [b = a] k[i]) (every
+ *   operation rounded once): new_label[i] = the allowed b != a of the row with the largest g(b), the lowest id among equals, where
+ *   g(b) > g(a); a otherwise.  Allowed: with size[a] == 1, any b with size[b] > 1, and b < a with size[b] == 1; with size[a] > 1,
+ *   b < a when round is even, b > a when it is odd.  own[i] = w_a + A_ii, moved[i] = 1 where new_label[i] != a.  stats[0] = the sum
+ *   of own, stats[1] = the number of movers: per workgroup in row order (part_sum, part_moved: meld_louvain_move_blocks(n, lanes)
+ *   elements each), then partial t, t + 256, ... per thread of one workgroup and a fixed tree.  tot[n], size[n]: the communities'
+ *   sums of k and numbers of vertices (meld_louvain_totals).  lanes: 16 or 64 per row (meld_louvain_lanes(n, nnz) picks 16 up to a
+ *   mean of 64 entries per row, one trip of a 16-lane group); a row of any length is served by either (quadratic in its length).  new_label must not be label.
+ * meld_louvain_totals: keys_sorted[n] = label << 32 | vertex ascending (meld_sort_pairs_u64_f64), vals_sorted[n] the vertices' k in
+ *   that order.  tot[b] = the sum over community b (element l, l + 64, ... of the segment per lane in order, then a xor butterfly; a
+ *   segment of one element is that element), size[b] its length, minm[b] its smallest vertex; 0 / 0 / -1 for a label in
+ *   [0, n_labels) that does not occur.
+ * meld_louvain_heads: flags[v] = 1 where minm[label[v]] == v (v is the smallest member of its community), else 0.
+ * meld_louvain_renumber: with rank[n + 1] the exclusive scan of flags, out[v] = rank[minm[label[v]]]: communities numbered by their
+ *   smallest member; sizes[out[v]] = size[label[v]] (int64, one store per community).
+ * meld_louvain_contract_keys: keys[e] = label[row of e] << 32 | label[col[e]] for every stored entry: sorted with the values next
+ *   to them (meld_sort_pairs_u64_f64), summed by key (meld_coo_merge) and assembled (meld_csr_from_keys) they are C^T A C.
+ * meld_modularity_terms: own[i] = the entries of row i whose column carries label[i] (the diagonal included), k[i] = all of them:
+ *   entry s, s + 16, ... per lane of 16 in order, then a xor butterfly.
+ *
+ * Each entry returns -1 before any launch for a NULL required pointer (a graph without entries passes any address for col and
+ * val), n outside [1, 2^31), lanes other than 16 and 64, a negative round, two_m or gamma not finite, gamma <= 0,
+ * new_label == label. */
+int meld_louvain_lanes(int64_t n, int64_t nnz);
+int64_t meld_louvain_move_blocks(int64_t n, int lanes);
+int meld_louvain_move(const int64_t* rowptr, const int32_t* col, const double* val, int64_t n, const int32_t* label, const double* k,
+                      const double* tot, const int32_t* size, double two_m, double gamma, int round, int lanes, int32_t* new_label,
+                      double* own, int32_t* moved, double* part_sum, int32_t* part_moved, double* stats, meld_stream_t stream);
+int meld_louvain_totals(const uint64_t* keys_sorted, const double* vals_sorted, int64_t n, int64_t n_labels, double* tot,
+                        int32_t* size, int32_t* minm, meld_stream_t stream);
+int meld_louvain_heads(const int32_t* label, const int32_t* minm, int64_t n, int32_t* flags, meld_stream_t stream);
+int meld_louvain_renumber(const int32_t* label, const int32_t* minm, const int64_t* rank, const int32_t* size, int64_t n,
+                          int32_t* out, int64_t* sizes, meld_stream_t stream);
+int meld_louvain_contract_keys(const int64_t* rowptr, const int32_t* col, int64_t n, const int32_t* label, uint64_t* keys,
+                               meld_stream_t stream);
+int meld_modularity_terms(const int64_t* rowptr, const int32_t* col, const double* val, int64_t n, const int32_t* label, double* own,
+                          double* k, meld_stream_t stream);
+
 /* ---- next#1: normalize_densities (meld/utils.py:35-47) ------------------------------------ */
 /* out[i,:] = in[i,:] / sum_j |in[i,j]|  (rows of zeros are copied unchanged, as sklearn does) */
 int meld_normalize_rows_l1(const double* in, double* out, int64_t n_rows, int p, meld_stream_t stream);

@@ -200,6 +200,14 @@ SIGNATURES = {
     "meld_landmark_gram": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _i32, _ptr, _ptr, _ptr, _ptr]),
     "meld_smacof_max_dim": (_i32, []),
     "meld_smacof_step": (_i32, [_ptr, _i64, _i32, _i32, _ptr, _ptr, _ptr, _ptr]),
+    "meld_louvain_lanes": (_i32, [_i64, _i64]),
+    "meld_louvain_move_blocks": (_i64, [_i64, _i32]),
+    "meld_louvain_move": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _f64, _f64, _i32, _i32, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "meld_louvain_totals": (_i32, [_ptr, _ptr, _i64, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "meld_louvain_heads": (_i32, [_ptr, _ptr, _i64, _ptr, _ptr]),
+    "meld_louvain_renumber": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr]),
+    "meld_louvain_contract_keys": (_i32, [_ptr, _ptr, _i64, _ptr, _ptr, _ptr]),
+    "meld_modularity_terms": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
 }
 
 

@@ -651,6 +651,37 @@ class DeviceGraph:
         sub.info["component"] = c
         return sub
 
+    # -- communities (meld_amd/louvain.py, csrc/louvain.hip): the "Louvain clusters" the reference's comparison takes from scanpy
+    # (comparison/comparison.py, find_n_clusters), by a deterministic synchronous rule.  Single-GPU graphs. ------------------------
+    def louvain_device(self, resolution=1.0, n_clusters=None, tol=1e-7, max_rounds=None, max_levels=None, recompute=False):
+        """``louvain`` (the same record; its ``labels_device`` and per-level labels never leave the GPU unless asked for)."""
+        from . import louvain
+
+        return louvain.louvain_device(self, resolution=resolution, n_clusters=n_clusters, tol=tol, max_rounds=max_rounds,
+                                      max_levels=max_levels, recompute=recompute)
+
+    def louvain(self, resolution=1.0, n_clusters=None, tol=1e-7, max_rounds=None, max_levels=None, recompute=False):
+        """Louvain communities of the cells: a ``LouvainRecord`` with ``labels`` (int32 ``[N]``, caller's order, communities
+        numbered by their smallest cell), ``labels_device``, ``n_communities``, ``sizes``, ``modularity``, ``resolution``,
+        ``levels`` (per level ``dict(vertices, communities, rounds, Q)``) and ``level_labels(l)``, the dendrogram.  Synchronous,
+        deterministic local moves (no random order, no floating-point atomics: the same bits every run, whatever ``perm``), then
+        contraction, until a level merges nothing; a level ends when the modularity did not rise by more than ``tol``, when
+        nothing moved, or after ``max_rounds`` (default 1000) rounds.  ``n_clusters=k`` bisects the resolution between 0.01 and 10
+        like the reference's ``find_n_clusters`` and returns the first partition with exactly ``k`` communities (ValueError
+        "r_start is too large" / "r_stop is too small" where the ends fail, and one naming the nearest counts when the interval
+        closes below 0.001).  A graph without entries gives ``N`` singletons with modularity 0.0; isolated cells stay alone.
+        ValueError on a row shard and for a resolution that is not finite and positive.  Kept on the graph per set of arguments."""
+        return self.louvain_device(resolution=resolution, n_clusters=n_clusters, tol=tol, max_rounds=max_rounds, max_levels=max_levels,
+                                   recompute=recompute)
+
+    def modularity(self, labels, resolution=1.0):
+        """``Q(labels; resolution) = (sum_c in_c - resolution sum_c tot_c^2 / 2m) / 2m`` of any labelling of the cells (host or
+        device integers, caller's order; the values need not be consecutive): ``networkx.community.modularity`` with
+        ``weight="weight"`` on a graph without self-loops.  ValueError for a wrong length or negative labels."""
+        from . import louvain
+
+        return louvain.modularity(self, labels, resolution=resolution)
+
 
 _BLAS_CTL = None
 

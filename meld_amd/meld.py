@@ -536,6 +536,18 @@ class MELD(GraphEstimator):
         index = getattr(getattr(self.graph, "_extend_state", None), "index", None)
         return pd.DataFrame(coords, index=index, columns=["PHATE{}".format(c + 1) for c in range(coords.shape[1])])
 
+    def louvain(self, **kwargs):
+        """Louvain communities of the fitted cells (what the reference's comparison takes from ``sc.tl.louvain``):
+        ``DeviceGraph.louvain(**kwargs).labels`` as a Series named ``"louvain"`` on the fitted cells' index; the record itself
+        (modularity, levels, the dendrogram) is ``op.graph.louvain(**kwargs)``, kept on the graph."""
+        if self.graph is None:
+            raise ValueError("Estimator must be `fit` before running `louvain`.")
+        if not hasattr(self.graph, "louvain"):
+            raise NotImplementedError("the graph of this estimator cannot find communities")
+        labels = self.graph.louvain(**kwargs).labels
+        index = getattr(getattr(self.graph, "_extend_state", None), "index", None)
+        return pd.Series(labels, index=index, name="louvain")
+
     def fit_transform(self, X, sample_labels, **kwargs):
         """Builds the graph on ``X`` and estimates the density of each sample in
         ``sample_labels`` (reference ``meld/meld.py:252-274``)."""
