@@ -384,7 +384,9 @@ __global__ __launch_bounds__(64) void metric_cross_seed_kernel(const double* __r
   const int64_t q = (int64_t)blockIdx.x * 64 + threadIdx.x;
   const double* __restrict__ xq = Qm + (q < M ? q : M - 1);  // (Qm [d][M]: transposed, as the search takes it)
   const int64_t t_lo = (int64_t)blockIdx.y * tiles_per_slice, t_hi = min(n_tiles, t_lo + tiles_per_slice);
-  double best = INFINITY;
+  // (compared AS fp32: with the fp64 minimum of the part rounded afterwards, two tiles whose bounds agree in fp32 went to the later
+  // one where its fp64 bound was lower, and the key depended on how the tiles were split over grid.y)
+  float best = INFINITY;
   int64_t bt = t_lo;
   for (int64_t t = t_lo; t < t_hi; ++t) {
     const double* __restrict__ blo = box_lo + t * d;
@@ -395,13 +397,14 @@ __global__ __launch_bounds__(64) void metric_cross_seed_kernel(const double* __r
       const double gk = fmax(0.0, fmax(blo[k] - x, x - bhi[k]));
       lb = (METRIC == MELD_METRIC_L1) ? lb + gk : fmax(lb, gk);
     }
-    if (lb < best) {
-      best = lb;
+    const float lf = (float)lb;
+    if (lf < best) {
+      best = lf;
       bt = t;
     }
   }
   if (q < M && t_lo < t_hi)
-    atomicMin(&seed_key[q], ((unsigned long long)__float_as_uint((float)best) << 32) | (unsigned long long)(uint32_t)bt);
+    atomicMin(&seed_key[q], ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(uint32_t)bt);
 }
 
 // the ksel smallest by (distance, column) of a query's n_slices ascending lists: one thread per query, a cursor per slice in LDS
