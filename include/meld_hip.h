@@ -760,6 +760,27 @@ int meld_kmeans_max_blocks(void);
 int meld_kmeans_assign(const double* X, int64_t n, int d, const double* centroids, int k, int32_t* labels,
                        double* part_sum, double* part_cnt, double* part_inertia, int n_blocks, meld_stream_t stream);
 
+/* ---- Lloyd step for thousands of centres (csrc/kmeans_wide.hip; meld_amd.KMeans, the reference's k-means baseline
+ *      comparison/comparison.py::run_geometry_clustering -> [UPSTREAM sklearn.cluster.KMeans]) -----------------------------
+ * Everything is fp64; no atomics; the same operands give the same bits every run.
+ * meld_kmeans_wide_assign: labels[i] (int32 [n]) = the centre nearest to row i of Y [n, d] (row-major, leading dimension
+ *   ldy >= d) among centres [k, d] (row-major, dense); best_d2[i] (NULL: not wanted) = the squared distance to it, clamped at 0.
+ *   Candidates are compared on |c_j|^2 - 2 y_i . c_j (fp64 matrix instruction); among equal scores the lowest index wins.
+ *   centre_norms [k] is written by the call (|c_j|^2) and read by its second launch.  1 <= d <= meld_kmeans_wide_max_d() = 128,
+ *   1 <= k <= meld_kmeans_wide_max_k() = 4096 per call (more centres: call per chunk and combine the minima).
+ * meld_kmeans_wide_sums: sums[j][:] (fp64 [k, d]) = the sum of the rows order[seg_ptr[j] .. seg_ptr[j + 1]) of Y; order int64 [n]
+ *   (a permutation of the rows grouped by label), seg_ptr int64 [k + 1] ascending in [0, n].  Any k >= 1.  The additions of a
+ *   cluster run in an order that depends on (order, seg_ptr) alone: 16 slots, slot s adds the groups s, s + 16, ... of 4
+ *   consecutive entries of the segment in sequence, the slots meet in slot order.  An empty segment gives zeros.
+ * Both return -1 before any launch for d or k out of range, ldy < d, n outside [0, 2^31) or a NULL required pointer;
+ * n == 0 is a successful no-op. */
+int meld_kmeans_wide_max_d(void);
+int meld_kmeans_wide_max_k(void);
+int meld_kmeans_wide_assign(const double* Y, int64_t ldy, int64_t n, int d, const double* centres, int k, double* centre_norms,
+                            int32_t* labels, double* best_d2, meld_stream_t stream);
+int meld_kmeans_wide_sums(const double* Y, int64_t ldy, int64_t n, int d, const int64_t* order, const int64_t* seg_ptr, int k,
+                          double* sums, meld_stream_t stream);
+
 /* ---- cache-locality ordering helper (no reference counterpart; csrc/reorder.hip) ---------- */
 /* out[i] = index (within its group) of the centroid nearest to X[i]; cents holds n_per_group
  * centroids per group, group[i] selects the group of point i (NULL = one shared set).  order

@@ -18,6 +18,7 @@ __all__ = [
     "get_meld_cmap",
     "normalize_densities",
     "VertexFrequencyCluster",
+    "KMeans",
     "Benchmarker",
     "utils",
     "filter",
@@ -31,6 +32,10 @@ def __getattr__(name):
         from .cluster import VertexFrequencyCluster
 
         return VertexFrequencyCluster
+    if name == "KMeans":  # k-means on the cells, one of the baselines the reference compares MELD against (comparison/comparison.py)
+        from .kmeans import KMeans
+
+        return KMeans
     if name == "Benchmarker":  # host-side helper of the reference package (meld/benchmark.py), lazy like the above
         from .benchmark import Benchmarker
 

@@ -155,6 +155,10 @@ SIGNATURES = {
     "meld_block_residuals_f64": (_i32, [_ptr, _ptr, _i64, _ptr, _i64, _i32, _ptr, _i32, _ptr, _ptr]),
     "meld_kmeans_max_blocks": (_i32, []),
     "meld_kmeans_assign": (_i32, [_ptr, _i64, _i32, _ptr, _i32, _ptr, _ptr, _ptr, _ptr, _i32, _ptr]),
+    "meld_kmeans_wide_max_d": (_i32, []),
+    "meld_kmeans_wide_max_k": (_i32, []),
+    "meld_kmeans_wide_assign": (_i32, [_ptr, _i64, _i64, _i32, _ptr, _i32, _ptr, _ptr, _ptr, _ptr]),
+    "meld_kmeans_wide_sums": (_i32, [_ptr, _i64, _i64, _i32, _ptr, _ptr, _i32, _ptr, _ptr]),
     "meld_scale_f64": (_i32, [_ptr, _f64, _ptr, _i64, _ptr]),
     "meld_axpby_f64": (_i32, [_f64, _ptr, _f64, _ptr, _i64, _ptr, _ptr]),
     "meld_normalize_rows_l1": (_i32, [_ptr, _ptr, _i64, _i32, _ptr]),

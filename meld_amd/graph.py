@@ -438,7 +438,7 @@ class DeviceGraph:
         raise NotImplementedError("the landmark operator (graphtools LandmarkGraph.landmark_op) is not implemented; "
                                   "MELD's density estimate does not use it")
 
-    def landmarks(self, n_landmark=None, clusters=None, n_svd=100, random_state=None, recompute=False):
+    def landmarks(self, n_landmark=None, clusters=None, n_svd=100, random_state=None, recompute=False, kmeans="library"):
         """graphtools' ``LandmarkGraph`` for this graph as a ``landmark.Landmarks`` record (``meld_amd/landmark.py``,
         ``csrc/landmark.hip``): ``clusters`` / ``clusters_device``, ``transitions`` (``[N, L]``) / ``transitions_device``,
         ``landmark_op`` (``[L, L]``) / ``landmark_op_device``, ``landmark_sums``, ``extend_to_data(Y)`` and ``interpolate(T, Y=None)``
@@ -448,16 +448,18 @@ class DeviceGraph:
         is the ``l``-th smallest label); otherwise the cells are clustered into at most ``n_landmark`` landmarks (default: the
         ``n_landmark`` the graph was fitted with) by k-means on ``diff_op @ V``, ``V`` the leading ``min(n_svd, n_landmark)`` singular
         vectors of the symmetric diffusion affinity from a seeded randomized range finder -- the same ``random_state`` gives the same labels.
+        ``kmeans``: ``"library"`` (the default: ``cluster._kmeans``) or ``"device"`` (k-means|| seeding and the Lloyd step of
+        ``csrc/kmeans_wide.hip``, ``meld_amd/kmeans.py``); part of the argument set, ValueError for any other value.
         ValueError without ``n_landmark`` and ``clusters``, for ``n_landmark >= N`` or above ``landmark.LANDMARK_MAX``, for bad
         ``clusters`` (TypeError for a dtype that is not integer) and on a row-sharded graph.  The ``landmark_op`` property of the
         graph itself stays unimplemented: the operator lives on the record."""
         from . import landmark
 
         return landmark.landmarks(self, n_landmark=n_landmark, clusters=clusters, n_svd=n_svd, random_state=random_state,
-                                  recompute=recompute)
+                                  recompute=recompute, kmeans=kmeans)
 
     def phate(self, n_components=2, t="auto", gamma=1, n_landmark=None, clusters=None, n_svd=100, mds="metric", max_iter=3000,
-              eps=1e-6, t_max=100, random_state=None, recompute=False):
+              eps=1e-6, t_max=100, random_state=None, recompute=False, kmeans="library"):
         """The PHATE embedding of this graph as a ``phate.PhateEmbedding`` record (``meld_amd/phate.py``, ``csrc/mds.hip``; [UPSTREAM
         phate ``PHATE.fit_transform``, unpinned: every stage is defined in ``meld_amd/phate.py``]): ``embedding`` (``[N,
         n_components]``, the caller's cell order) / ``embedding_device``, ``landmark_embedding``, ``t``, ``entropy``,
@@ -476,7 +478,7 @@ class DeviceGraph:
         from . import phate
 
         return phate.phate(self, n_components=n_components, t=t, gamma=gamma, n_landmark=n_landmark, clusters=clusters, n_svd=n_svd,
-                           mds=mds, max_iter=max_iter, eps=eps, t_max=t_max, random_state=random_state, recompute=recompute)
+                           mds=mds, max_iter=max_iter, eps=eps, t_max=t_max, random_state=random_state, recompute=recompute, kmeans=kmeans)
 
     def kernel_diagonal(self):
         """Diagonal of the kernel matrix K in the device order: K_ii = 1 / (ksum_i^2)^anisotropy for a

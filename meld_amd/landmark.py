@@ -35,7 +35,7 @@ import numpy as np
 from ._graph_steps import require_unsharded
 
 __all__ = ["LANDMARK_MAX", "Landmarks", "check_n_landmark", "compact_labels", "check_clusters", "merge_by_label", "spectral_features",
-           "default_clusters", "landmarks"]
+           "default_clusters", "check_kmeans", "landmarks"]
 
 LANDMARK_MAX = 4096  # ``meld_landmark_max()``: the Gram's LDS accumulator (tests/test_landmark_host.py holds the two together)
 OVERSAMPLE = 10  # columns of the range finder beyond n_svd
@@ -203,7 +203,7 @@ def spectral_features(G, n_landmark, n_svd=100, random_state=None, info=None):
     return diffuse_device(G, V.contiguous(), t=1, device_order=True)
 
 
-def default_clusters(G, n_landmark, n_svd=100, random_state=None, info=None):
+def default_clusters(G, n_landmark, n_svd=100, random_state=None, info=None, kmeans="library"):
     """Labels of the default clustering, an int64 device tensor ``[N]`` in the caller's order (not compacted): graphtools' recipe
     -- k-means on ``diff_op @ V``, ``V`` the leading ``n_svd`` singular vectors of ``diff_aff = D^-1/2 K D^-1/2`` -- from existing
     kernels and library calls: ``diff_aff x = sqrt(r) * diffuse_step(x / sqrt(r))``; a seeded Gaussian ``[N, n_svd + 10]``, power
@@ -220,21 +220,31 @@ def default_clusters(G, n_landmark, n_svd=100, random_state=None, info=None):
     directions, and the surplus hides them -- on four disconnected blobs of 200 cells the 96 further columns of ``n_svd = 100``
     carry 20 times the variance of the four that tell the blobs apart (within-blob inertia 60.96 of 63.96 in total: the blobs
     are the best partition by 1.5 %, and neither this k-means nor sklearn's finds it from a k-means++ start), while on four
-    columns every start does.  Upstream's default (2,000 landmarks, 100 vectors) is not touched by the clip."""
-    import torch
+    columns every start does.  Upstream's default (2,000 landmarks, 100 vectors) is not touched by the clip.
 
-    from .cluster import _kmeans
+    ``kmeans="device"`` clusters the same features with ``kmeans.kmeans_device`` (k-means|| seeding, the Lloyd step of
+    ``csrc/kmeans_wide.hip``) under the same seed and iteration cap; ``"library"`` is ``cluster._kmeans``, as before."""
+    import torch
 
     features = spectral_features(G, n_landmark, n_svd=n_svd, random_state=random_state, info=info)
     km = {}
-    lab = _kmeans(features, int(n_landmark), n_init=1, max_iter=KMEANS_MAX_ITER, seed=0 if random_state is None else int(random_state),
-                  info=km)
+    seed = 0 if random_state is None else int(random_state)
+    if kmeans == "device":
+        from .kmeans import kmeans_device
+
+        lab = kmeans_device(features, int(n_landmark), n_init=1, max_iter=KMEANS_MAX_ITER, seed=seed, info=km)["labels"].to(torch.int64)
+    else:
+        from .cluster import _kmeans
+
+        lab = _kmeans(features, int(n_landmark), n_init=1, max_iter=KMEANS_MAX_ITER, seed=seed, info=km)
     if G.perm is not None:  # (device row v is the caller's cell perm[v])
         out = torch.empty_like(lab)
         out[G.perm] = lab
         lab = out
     if info is not None:
         info.update(kmeans_iterations=km.get("iterations"))
+        if kmeans == "device":
+            info.update(kmeans="device")
     return lab
 
 
@@ -337,9 +347,18 @@ def _build(G, compact, L, info):
     return Landmarks(G, compact, L, A, op, s, info)
 
 
-def landmarks(G, n_landmark=None, clusters=None, n_svd=100, random_state=None, recompute=False):
+def check_kmeans(kmeans):
+    """``kmeans`` as one of ``"library"`` (``cluster._kmeans``) and ``"device"`` (``kmeans.kmeans_device``); ValueError otherwise."""
+    if not isinstance(kmeans, str) or kmeans not in ("library", "device"):
+        raise ValueError("kmeans must be 'library' or 'device', got {!r}".format(kmeans))
+    return kmeans
+
+
+def landmarks(G, n_landmark=None, clusters=None, n_svd=100, random_state=None, recompute=False, kmeans="library"):
     """``DeviceGraph.landmarks``: the ``Landmarks`` record for the given labels, or for the default clustering into ``n_landmark``
-    (default: the ``n_landmark`` the graph was fitted with); kept on the graph per argument set."""
+    (default: the ``n_landmark`` the graph was fitted with); kept on the graph per argument set.  ``kmeans``: which k-means the
+    default clustering runs, ``"library"`` (the default) or ``"device"``; part of the argument set."""
+    check_kmeans(kmeans)
     if n_landmark is None and clusters is None:
         n_landmark = getattr(G, "n_landmark", None)
         if n_landmark is None:
@@ -354,13 +373,15 @@ def landmarks(G, n_landmark=None, clusters=None, n_svd=100, random_state=None, r
         if isinstance(n_svd, (bool, np.bool_)) or not isinstance(n_svd, (numbers.Integral, np.integer)) or int(n_svd) < 1:
             raise ValueError("n_svd must be a positive integer, got {!r}".format(n_svd))
         key = ("default", n_landmark, int(n_svd), None if random_state is None else int(random_state))
+        if kmeans != "library":  # (the default route keeps the key it always had)
+            key = key + (kmeans,)
     cache = G.__dict__.setdefault("_landmarks", {})
     if recompute:
         cache.pop(key, None)
     if key not in cache:
         if clusters is None:
             info = dict(clustering="default")
-            lab = default_clusters(G, n_landmark, n_svd=n_svd, random_state=random_state, info=info)
+            lab = default_clusters(G, n_landmark, n_svd=n_svd, random_state=random_state, info=info, kmeans=kmeans)
             compact, values = compact_labels(lab.cpu().numpy())
             L = int(values.shape[0])
         cache[key] = _build(G, compact, L, info)

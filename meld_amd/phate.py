@@ -356,11 +356,12 @@ def _compute(G, lm, a, info):
 
 
 def phate(G, n_components=2, t="auto", gamma=1, n_landmark=None, clusters=None, n_svd=100, mds="metric", max_iter=3000, eps=1e-6,
-          t_max=100, random_state=None, recompute=False):
+          t_max=100, random_state=None, recompute=False, kmeans="library"):
     """``DeviceGraph.phate``: the ``PhateEmbedding`` record of the graph for the given arguments, kept on the graph per argument
-    set."""
+    set (``kmeans``: the k-means of the default landmark clustering, ``landmarks()``'s argument)."""
     from . import landmark
 
+    landmark.check_kmeans(kmeans)
     a = check_arguments(n_components=n_components, t=t, gamma=gamma, mds=mds, max_iter=max_iter, eps=eps, t_max=t_max)
     require_unsharded(G, "the PHATE embedding is")
     if n_landmark is None:
@@ -379,11 +380,13 @@ def phate(G, n_components=2, t="auto", gamma=1, n_landmark=None, clusters=None, 
         lm, route = None, ("direct",)
     else:
         lm = G.landmarks(n_landmark=None if clusters is not None else n_landmark, clusters=clusters, n_svd=n_svd, random_state=random_state,
-                         recompute=recompute)
+                         recompute=recompute, kmeans=kmeans)
         if clusters is not None:
             route = ("clusters", hashlib.sha1(lm.clusters.tobytes()).hexdigest())
         else:
             route = ("default", int(n_landmark), int(n_svd), None if random_state is None else int(random_state))
+            if kmeans != "library":
+                route = route + (kmeans,)
     key = route + tuple(a[name] for name in ("n_components", "t", "gamma", "mds", "max_iter", "eps", "t_max"))
     cache = G.__dict__.setdefault("_phate", {})
     if recompute:
