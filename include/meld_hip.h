@@ -1029,6 +1029,32 @@ int meld_louvain_contract_keys(const int64_t* rowptr, const int32_t* col, int64_
 int meld_modularity_terms(const int64_t* rowptr, const int32_t* col, const double* val, int64_t n, const int32_t* label, double* own,
                           double* k, meld_stream_t stream);
 
+/* ---- Leiden communities: the refinement of a level's move partition (csrc/leiden.hip; the reference clusters its cells with
+ *      scanpy's leiden in comparison/comparison.py, find_n_clusters) ------------------------------------------------------------
+ * The graph, k and two_m as for Louvain.  comm[n]: the communities of the move partition, int32 in [0, n), tot_comm[n] their sums of
+ * k addressed by label; sub[n]: the sub-communities, int32 in [0, n) (ids are vertex numbers, a label that occurs contains the
+ * vertex of that number), tot[n] and size[n] their sums of k and sizes (meld_louvain_totals for both).
+ *
+ * meld_leiden_propose: prop[v] = -1 unless size[sub[v]] == 1 and inC_v two_m >= (gamma k[v]) (tot_comm[comm[v]] - k[v]), inC_v the
+ *   entries A_vj, j != v, comm[j] == comm[v], added in storage order.  Otherwise, over those entries, w_t = the ones with
+ *   sub[j] == t added in storage order, g(t) = w_t two_m - (gamma k[v]) tot[t] (every operation rounded once), and t is allowed if
+ *   size[t] >= 2 or pri(t, round) < pri(v, round) with pri(x, r): x += r 0x9E3779B9; twice x = (x ^ x >> 16) 0x45D9F3B; x ^= x >> 16
+ *   (mod 2^32, unsigned).  prop[v] = the allowed t != sub[v] with the largest g(t) > 0, the lowest t among equals; -1 if none.
+ *   lanes: 16 or 64 per row (meld_louvain_lanes); a row of any length is served by either.
+ * meld_leiden_commit: new_sub[v] = prop[v] where prop[v] is in [0, n) and (size[prop[v]] >= 2 or prop[prop[v]] < 0), sub[v]
+ *   elsewhere.  movers[0] = how many moved: per workgroup (part_moved: meld_leiden_commit_blocks(n) elements) by a fixed tree,
+ *   then the workgroups' counts by one workgroup in a fixed order.
+ *
+ * Each entry returns -1 before any launch for a NULL required pointer (a graph without entries passes any address for col and
+ * val), n outside [1, 2^31), lanes other than 16 and 64, a negative round, two_m or gamma not finite, gamma <= 0, and an output
+ * that is one of the int32 inputs. */
+int64_t meld_leiden_commit_blocks(int64_t n);
+int meld_leiden_propose(const int64_t* rowptr, const int32_t* col, const double* val, int64_t n, const int32_t* comm,
+                        const int32_t* sub, const double* k, const double* tot, const int32_t* size, const double* tot_comm,
+                        double two_m, double gamma, int round, int lanes, int32_t* prop, meld_stream_t stream);
+int meld_leiden_commit(const int32_t* sub, const int32_t* prop, const int32_t* size, int64_t n, int32_t* new_sub, int32_t* part_moved,
+                       int64_t* movers, meld_stream_t stream);
+
 /* ---- next#1: normalize_densities (meld/utils.py:35-47) ------------------------------------ */
 /* out[i,:] = in[i,:] / sum_j |in[i,j]|  (rows of zeros are copied unchanged, as sklearn does) */
 int meld_normalize_rows_l1(const double* in, double* out, int64_t n_rows, int p, meld_stream_t stream);

@@ -19,6 +19,7 @@ __all__ = [
     "normalize_densities",
     "VertexFrequencyCluster",
     "KMeans",
+    "LeidenRecord",
     "Benchmarker",
     "utils",
     "filter",
@@ -36,6 +37,10 @@ def __getattr__(name):
         from .kmeans import KMeans
 
         return KMeans
+    if name == "LeidenRecord":  # what ``DeviceGraph.leiden`` / ``op.graph.leiden`` return (lazy: the module imports torch)
+        from .leiden import LeidenRecord
+
+        return LeidenRecord
     if name == "Benchmarker":  # host-side helper of the reference package (meld/benchmark.py), lazy like the above
         from .benchmark import Benchmarker
 

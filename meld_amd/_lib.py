@@ -212,6 +212,9 @@ SIGNATURES = {
     "meld_louvain_renumber": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr]),
     "meld_louvain_contract_keys": (_i32, [_ptr, _ptr, _i64, _ptr, _ptr, _ptr]),
     "meld_modularity_terms": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "meld_leiden_commit_blocks": (_i64, [_i64]),
+    "meld_leiden_propose": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f64, _f64, _i32, _i32, _ptr, _ptr]),
+    "meld_leiden_commit": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
 }
 
 

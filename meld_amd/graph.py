@@ -676,6 +676,24 @@ class DeviceGraph:
         return self.louvain_device(resolution=resolution, n_clusters=n_clusters, tol=tol, max_rounds=max_rounds, max_levels=max_levels,
                                    recompute=recompute)
 
+    # -- Leiden communities (meld_amd/leiden.py, csrc/leiden.hip): the Louvain run with a refinement of every level's partition, so
+    # that every community is connected (find_n_clusters(adata, k, "leiden") of the reference's comparison). -----------------------
+    def leiden(self, resolution=1.0, n_clusters=None, tol=1e-7, max_rounds=None, max_levels=None, recompute=False):
+        """Leiden communities of the cells: a ``LeidenRecord`` with the attributes of ``louvain``'s record (``labels``,
+        ``labels_device``, ``n_communities``, ``sizes``, ``modularity``, ``resolution``, ``level_labels(l)``) and ``levels`` holding
+        per level ``dict(vertices, communities, subcommunities, rounds, refine_rounds, Q)``.  The run is ``louvain``'s with a
+        refinement between a level's moves and its contraction: inside every community the vertices merge again from singletons,
+        a vertex joining only a sub-community it has an entry to and nobody leaving one of two or more, and the graph is
+        contracted by those sub-communities.  Every community of a run that ends on its own induces a connected subgraph (a run
+        cut by ``max_levels`` returns the last move partition, without that guarantee).  Synchronous and deterministic: the same
+        bits every run, whatever ``perm``; upstream's randomised choice is not offered.  ``max_rounds`` bounds the rounds of a
+        move phase and of a refinement alike.  ``n_clusters``, the graph without entries, row shards and the argument checks: as
+        for ``louvain``.  Kept on the graph per set of arguments."""
+        from . import leiden
+
+        return leiden.leiden_device(self, resolution=resolution, n_clusters=n_clusters, tol=tol, max_rounds=max_rounds,
+                                    max_levels=max_levels, recompute=recompute)
+
     def modularity(self, labels, resolution=1.0):
         """``Q(labels; resolution) = (sum_c in_c - resolution sum_c tot_c^2 / 2m) / 2m`` of any labelling of the cells (host or
         device integers, caller's order; the values need not be consecutive): ``networkx.community.modularity`` with

@@ -135,13 +135,14 @@ def _degrees(lib, st, rowptr, val, n):
     return k
 
 
-def _run_level(lib, st, rowptr, col, val, k, two_m, gamma, tol, max_rounds):
-    """The rounds of one level from singletons: ``(labels kept, Q, rounds)``."""
+def _run_level(lib, st, rowptr, col, val, k, two_m, gamma, tol, max_rounds, start=None):
+    """The rounds of one level from singletons, or from the labels ``start`` (int32 ids in ``[0, n)``; the Leiden run starts a
+    level from the partition of the level before): ``(labels kept, Q, rounds)``."""
     n, dev = int(k.shape[0]), k.device
     ar = torch.arange(n, dtype=torch.int64, device=dev)
     lanes = int(lib.meld_louvain_lanes(n, int(col.shape[0])))
     blocks = int(lib.meld_louvain_move_blocks(n, lanes))
-    c = ar.to(torch.int32)
+    c = ar.to(torch.int32) if start is None else start
     own = torch.empty(n, dtype=torch.float64, device=dev)
     part_sum = torch.empty(blocks, dtype=torch.float64, device=dev)
     part_moved = torch.empty(blocks, dtype=torch.int32, device=dev)
@@ -241,28 +242,24 @@ def _run(G, gamma, tol, max_rounds, max_levels):
     return LouvainRecord(cell, sizes.cpu().numpy(), q, gamma, levels, level_labels)
 
 
-def louvain_device(G, resolution=1.0, n_clusters=None, tol=DEFAULT_TOL, max_rounds=None, max_levels=None, recompute=False):
-    """The Louvain record of ``G`` (see ``DeviceGraph.louvain``); nothing but three numbers per round and the counts of a level
-    goes through the host.  Kept on the graph per set of arguments."""
+def _check_run_arguments(G, what, resolution, n_clusters, tol, max_rounds, max_levels):
+    """The arguments of a community run, checked before anything touches the device: ``(gamma, n_clusters, tol, max_rounds,
+    max_levels)`` with the defaults filled in."""
     gamma = _check_resolution(resolution)
     n_clusters = _positive_int("n_clusters", n_clusters, None)
     max_rounds = _positive_int("max_rounds", max_rounds, DEFAULT_MAX_ROUNDS)
     max_levels = _positive_int("max_levels", max_levels, DEFAULT_MAX_LEVELS)
     if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol >= 0:
         raise ValueError("tol must be a number >= 0, got {!r}".format(tol))
-    tol = float(tol)
-    require_unsharded(G, "Louvain communities are")
-    kept = G.__dict__.setdefault("_louvain", {})
+    require_unsharded(G, what)
+    return gamma, n_clusters, float(tol), max_rounds, max_levels
 
-    def run(g):
-        key = (g, tol, max_rounds, max_levels)
-        if recompute or key not in kept:
-            kept[key] = _run(G, g, tol, max_rounds, max_levels)
-        return kept[key]
 
+def _for_n_clusters(run, gamma, n_clusters):
+    """``run(gamma)``, or for a wanted number of communities the record of the resolution that gives it: the bisection of
+    find_n_clusters (reference comparison/comparison.py), iteratively.  ``run(g)`` returns a record with ``n_communities``."""
     if n_clusters is None:
         return run(gamma)
-    # the bisection of find_n_clusters (reference comparison/comparison.py), iteratively
     lo, hi = R_START, R_STOP
     rec = run(lo)
     n_lo = rec.n_communities
@@ -287,6 +284,22 @@ def louvain_device(G, resolution=1.0, n_clusters=None, tol=DEFAULT_TOL, max_roun
             hi, n_hi = mid, rec.n_communities
     raise ValueError("no resolution between {} and {} gives {} communities: the nearest counts found are {} (resolution {:g}) and {} "
                      "(resolution {:g})".format(R_START, R_STOP, n_clusters, n_lo, lo, n_hi, hi))
+
+
+def louvain_device(G, resolution=1.0, n_clusters=None, tol=DEFAULT_TOL, max_rounds=None, max_levels=None, recompute=False):
+    """The Louvain record of ``G`` (see ``DeviceGraph.louvain``); nothing but three numbers per round and the counts of a level
+    goes through the host.  Kept on the graph per set of arguments."""
+    gamma, n_clusters, tol, max_rounds, max_levels = _check_run_arguments(G, "Louvain communities are", resolution, n_clusters, tol,
+                                                                          max_rounds, max_levels)
+    kept = G.__dict__.setdefault("_louvain", {})
+
+    def run(g):
+        key = (g, tol, max_rounds, max_levels)
+        if recompute or key not in kept:
+            kept[key] = _run(G, g, tol, max_rounds, max_levels)
+        return kept[key]
+
+    return _for_n_clusters(run, gamma, n_clusters)
 
 
 def louvain(G, **kwargs):

@@ -548,6 +548,18 @@ class MELD(GraphEstimator):
         index = getattr(getattr(self.graph, "_extend_state", None), "index", None)
         return pd.Series(labels, index=index, name="louvain")
 
+    def leiden(self, **kwargs):
+        """Leiden communities of the fitted cells (what the reference's comparison takes from ``sc.tl.leiden``):
+        ``DeviceGraph.leiden(**kwargs).labels`` as a Series named ``"leiden"`` on the fitted cells' index; the record itself
+        (modularity, levels, the dendrogram) is ``op.graph.leiden(**kwargs)``, kept on the graph."""
+        if self.graph is None:
+            raise ValueError("Estimator must be `fit` before running `leiden`.")
+        if not hasattr(self.graph, "leiden"):
+            raise NotImplementedError("the graph of this estimator cannot find communities")
+        labels = self.graph.leiden(**kwargs).labels
+        index = getattr(getattr(self.graph, "_extend_state", None), "index", None)
+        return pd.Series(labels, index=index, name="leiden")
+
     def fit_transform(self, X, sample_labels, **kwargs):
         """Builds the graph on ``X`` and estimates the density of each sample in
         ``sample_labels`` (reference ``meld/meld.py:252-274``)."""
