@@ -1086,6 +1086,56 @@ int meld_csr_transpose_keys(const int64_t* rowptr, const int32_t* col, const voi
 int meld_csr_rows_to_dense_f64(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t row_begin,
                                int64_t n_rows, int64_t n_cols, double* out, int64_t ldo, meld_stream_t stream);
 
+/* ---- rank-sum differential expression on the CSC copy of the data (csrc/ranksum.hip; the reference ends its analyses with
+ *      de.test.two_sample(..., test='rank') per gene, notebooks/MELD_thresholding.Tcell.ipynb) ------------------------------------
+ * The operand is the CSR of X^T: rowptr[n_genes + 1] int64, col[nnz] int32 cell indices (no cell twice in a gene), val[nnz] fp32
+ * (val_f32 = 1, widened exactly) or fp64, finite.  code[n_cells] int32: the class of each cell in [0, k), anything else (-1): the
+ * cell takes no part.  ncls[k] int64: the class sizes, m their sum (at most MELD_RANKSUM_MAX_SELECTED: the cube of a tie group's
+ * size is taken in int64; every entry that takes m refuses more).  Stored entries equal to zero (+0.0, -0.0) count as zeros.
+ *
+ * Per gene g, over the m selected cells ranked with mid-ranks (implicit zeros included, negatives below them):
+ *   rank2[g * k + c] int64: twice the rank sum of class c;      tie[g] int64: the sum of t^3 - t over all tie groups;
+ *   nnz[g * k + c] int32: the selected non-zero entries of class c;      sum[g * k + c] fp64: the sum of the class's values.
+ * rank2, tie and nnz are integer arithmetic throughout (integer LDS atomics: any order gives the same bits), the same whichever
+ * route computes them.  sum: thread t of 128 adds the entries t, t + 128, ... of the gene in storage order, then a fixed tree over
+ * the 128 partial sums; one kernel for every gene.  No floating-point atomics.
+ *
+ * meld_ranksum_short: the genes genes[n_list] (int32, each of stored length <= meld_ranksum_lds_max(); a longer one is not
+ *   computed, its outputs are set to -1): gathered, sorted and scanned in LDS, one workgroup per gene.
+ * meld_ranksum_gather: for the genes genes[n_list] of any length, with off[n_list + 1] the exclusive scan of their stored lengths
+ *   and total = off[n_list]: keys[e] = the order-preserving 64-bit image of the value (sign bit set for positives, all bits
+ *   flipped for negatives), payload[e] = slot << 32 | class for entry e - off[slot] of gene genes[slot]; an entry that takes no
+ *   part has the image ~0 and the class 0xFFFFFFFF.
+ * meld_sort_pairs_u64_u64: stable radix sort of (u64 key, u64 value) pairs on the key bits [begin_bit, end_bit); temp as for
+ *   meld_sort_pairs_u64_f64 (meld_sort_temp_bytes(n); checked).  Sorting the gathered pairs by image and then, payload as key, on
+ *   the slot bits [32, 64) leaves every gene's segment at off[slot], ascending by value, the dead entries last.
+ * meld_ranksum_scan: rank2, tie and nnz of the genes genes[n_list] from those sorted arrays, one workgroup per gene.
+ * meld_ranksum_sums: sum of every gene.
+ *
+ * Each entry returns -1 before any launch, naming itself, for a NULL required pointer, val_f32 outside {0, 1}, n_genes or n_cells
+ * outside [1, 2^31), k outside [1, meld_ranksum_max_classes()], m outside [0, MELD_RANKSUM_MAX_SELECTED], n_list outside its range,
+ * total outside [0, 2^38), a sort whose temp is too small.  Cell indices and classes are range-checked inside the kernels before
+ * they address anything. */
+#define MELD_RANKSUM_LDS_MAX 4096
+#define MELD_RANKSUM_MAX_CLASSES 64
+#define MELD_RANKSUM_MAX_SELECTED 2097151ll
+int meld_ranksum_lds_max(void);
+int meld_ranksum_max_classes(void);
+int64_t meld_ranksum_max_selected(void);
+int meld_ranksum_sums(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t n_genes, const int32_t* code,
+                      int64_t n_cells, int k, double* sum, meld_stream_t stream);
+int meld_ranksum_short(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t n_genes, const int32_t* genes,
+                       int64_t n_list, const int32_t* code, int64_t n_cells, int k, const int64_t* ncls, int64_t m, int64_t* rank2,
+                       int64_t* tie, int32_t* nnz, meld_stream_t stream);
+int meld_ranksum_gather(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t n_genes, const int32_t* genes,
+                        const int64_t* off, int64_t n_list, int64_t total, const int32_t* code, int64_t n_cells, int k, uint64_t* keys,
+                        uint64_t* payload, meld_stream_t stream);
+int meld_sort_pairs_u64_u64(const uint64_t* keys_in, uint64_t* keys_out, const uint64_t* vals_in, uint64_t* vals_out, int64_t n,
+                            int begin_bit, int end_bit, void* temp, size_t temp_bytes, meld_stream_t stream);
+int meld_ranksum_scan(const uint64_t* keys_sorted, const uint64_t* payload_sorted, const int32_t* genes, const int64_t* off,
+                      int64_t n_list, int64_t n_genes, int k, const int64_t* ncls, int64_t m, int64_t* rank2, int64_t* tie, int32_t* nnz,
+                      meld_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,7 @@ __all__ = [
     "VertexFrequencyCluster",
     "KMeans",
     "LeidenRecord",
+    "rank_sum_test",
     "Benchmarker",
     "utils",
     "filter",
@@ -41,6 +42,10 @@ def __getattr__(name):
         from .leiden import LeidenRecord
 
         return LeidenRecord
+    if name == "rank_sum_test":  # which genes differ between groups of cells (the reference: de.test.two_sample(..., test='rank'))
+        from .diffexp import rank_sum_test
+
+        return rank_sum_test
     if name == "Benchmarker":  # host-side helper of the reference package (meld/benchmark.py), lazy like the above
         from .benchmark import Benchmarker
 

@@ -215,6 +215,14 @@ SIGNATURES = {
     "meld_leiden_commit_blocks": (_i64, [_i64]),
     "meld_leiden_propose": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr, _ptr, _ptr, _f64, _f64, _i32, _i32, _ptr, _ptr]),
     "meld_leiden_commit": (_i32, [_ptr, _ptr, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "meld_ranksum_lds_max": (_i32, []),
+    "meld_ranksum_max_classes": (_i32, []),
+    "meld_ranksum_max_selected": (_i64, []),
+    "meld_ranksum_sums": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _ptr, _i64, _i32, _ptr, _ptr]),
+    "meld_ranksum_short": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _ptr, _i64, _ptr, _i64, _i32, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "meld_ranksum_gather": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _ptr, _ptr, _i64, _i64, _ptr, _i64, _i32, _ptr, _ptr, _ptr]),
+    "meld_sort_pairs_u64_u64": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _i32, _i32, _ptr, _sz, _ptr]),
+    "meld_ranksum_scan": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i32, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
 }
 
 

@@ -560,6 +560,21 @@ class MELD(GraphEstimator):
         index = getattr(getattr(self.graph, "_extend_state", None), "index", None)
         return pd.Series(labels, index=index, name="leiden")
 
+    def rank_sum_test(self, data, groups=None, group=None, reference=None, gene_names=None):
+        """Which genes differ between groups of cells: the Wilcoxon rank-sum test per gene on the device
+        (``meld_amd.diffexp.rank_sum_test``; the reference's notebooks end with ``de.test.two_sample(..., test='rank')``).
+        ``groups``: one label per cell -- clusters, thresholded likelihoods, ...; omitted after ``transform``, the cells' sample
+        labels are used.  ``data`` (cells x genes) is always passed: ``fit`` keeps the graph, not the expression matrix -- the
+        device CSR matrix is dropped once it is reduced -- so hold a ``DeviceCSR`` yourself to test it more than once without
+        another upload and transpose."""
+        from .diffexp import rank_sum_test
+
+        if groups is None:
+            groups = getattr(self, "_sample_labels", None)
+            if groups is None:
+                raise ValueError("rank_sum_test: pass `groups`, or run `transform` first to test between the sample labels")
+        return rank_sum_test(data, groups, group=group, reference=reference, gene_names=gene_names)
+
     def fit_transform(self, X, sample_labels, **kwargs):
         """Builds the graph on ``X`` and estimates the density of each sample in
         ``sample_labels`` (reference ``meld/meld.py:252-274``)."""
