@@ -286,7 +286,10 @@ int meld_knn16_finish_rows(float* cand_d2, int32_t* cand_idx, int32_t* cand_cnt,
  * (wave, tile) pair is tested on K block 0 alone against the row's START threshold (thr_init, scaled units: the seeds the lists
  * were built for) and loses its bit when no partial distance is within reach; step_list is rewritten in place, emptied entries
  * dropped, cnt_out[block] = the new length (may alias step_cnt), tested (optional) += pairs tested.  meld_knn16_topk_listed over
- * the thinned lists returns the rows the search over the full ones would (no reference counterpart: graphtools searches a tree). */
+ * the thinned lists returns the rows the search over the full ones would (no reference counterpart: graphtools searches a tree).
+ * list_stride is at least the number of tiles of Rt16, as every list builder requires (a list holds a tile at most once), so it
+ * bounds the tile numbers: where list_stride tiles are shorter than 4 GiB the kernel addresses all of them through one buffer
+ * descriptor, otherwise through one per staged piece. */
 int meld_knn16_partial_filter(const void* Q16, const float* Qn, const void* Rt16, const float* scale_info, const float* norm2_max, int d,
                               int64_t q_count, const float* thr_init, uint32_t* step_list, const int32_t* step_cnt, int64_t list_stride,
                               int32_t* cnt_out, uint64_t* tested, const int32_t* block_order /* optional: workgroup g takes block

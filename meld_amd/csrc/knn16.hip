@@ -1144,14 +1144,26 @@ __attribute__((amdgpu_waves_per_eu(k16_waves(KB, NPROD, EE), k16_waves(KB, NPROD
 // no staging at all -- every wave walking the list on its own, its A fragments by 16-byte loads straight from global memory, four
 // live entries and eight loads in flight, no barrier before the rewrite: 7.4 ms at four waves per SIMD, 7.9-8.1 at six; one copy
 // request behind every other tile's test instead of the four of a wave back to back at the top of the step: 5.6 against 5.6)
-template <int TPS, int WPE>  // tiles per step (and barrier); waves per SIMD the kernel is compiled for
+// The pair tests of a step.  A wave forms the set of the step's tiles that list it ONCE -- one ballot over the register of entries,
+// a scalar mask -- and walks it with s_ff1, software-pipelined over two accumulator sets of 32 registers: the A fragments of pair
+// p + 1 are requested before the verdict of pair p is formed, and the group-0 MFMAs of pair p + 1 (set X) are issued before group 1 of
+// pair p (set Y) is computed and reduced, so the reduction of X at the top of the next pair reads results that are a pair old and no
+// LDS round trip stands bare in front of an MFMA; the pipeline drains at the end of the step's live set, nothing is carried across
+// the barrier.  The verdict is wave-uniform: each group's compare mask is a scalar, the keep bit is (mask0 | mask1) != 0, and group 1
+// is not computed at all when some lane of group 0 hit (a uniform branch; it pays on the kept pairs, a quarter of all).  (Before:
+// eight readlane / test / branch rounds per step, the two ds_read_b128 of a pair issued behind the verdict of the pair before,
+// `hit0 || hit1` compiled as a lane-divergent short circuit that never skipped anything.)
+// ONE_DESC: the pieces are staged from ONE buffer descriptor over the whole Rt16 array (n_tiles tiles; the launcher takes this form
+// where the array is shorter than 4 GiB), a piece addressed by its scalar offset = tile * tile_bytes + plane * 2048 and its LDS
+// destination by a constant added to the wave's ring base; otherwise a descriptor per piece, as before.
+template <int TPS, int WPE, bool ONE_DESC>  // tiles per step (and barrier); waves per SIMD the kernel is compiled for
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void knn16_partial_filter_kernel(const _Float16* __restrict__ Q16, const float* __restrict__ Qn,
                                                                    const _Float16* __restrict__ Rt16, const float* __restrict__ scale_info,
                                                                    const float* __restrict__ norm2_max, const float* __restrict__ thr_init,
                                                                    unsigned* step_list, const int* __restrict__ step_cnt, long long list_stride,
                                                                    int* __restrict__ cnt_out, unsigned long long* __restrict__ tested,
-                                                                   const int* __restrict__ block_order, int KB, int ee_hi) {
-  static_assert(TPS >= 2 && TPS <= 32 && (TPS & 1) == 0, "tiles per step");
+                                                                   const int* __restrict__ block_order, int KB, int ee_hi, unsigned n_tiles) {
+  static_assert(TPS >= 4 && TPS <= 32 && (TPS & 3) == 0, "tiles per step");
   __shared__ __attribute__((aligned(16))) _Float16 ring[2][TPS][2 * K16_TS * 8];  // K block 0, hi planes: [k-half][ref][8 halves]
   __shared__ unsigned wmask[2][4];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -1203,19 +1215,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     const int idx = step * TPS + lane;
     return (lane < TPS && idx < n) ? my_list_w[idx] : 0u;
   };
-  // staging: 2 TPS pieces of 1 KiB per step, TPS / 2 per wave: piece k = plane (k & 1) of the step's tile (k >> 1)
+  // staging: 2 TPS pieces of 1 KiB per step, TPS / 2 per wave: the two planes of the step's tiles wave * TPS / 4 ...
+  // the whole array behind one descriptor (ONE_DESC; n_tiles * tile_bytes < 4 GiB: the launcher), and this wave's part of the ring
+  const i32x4 rsrc_all = {(int)(unsigned)src_base, (int)((src_base >> 32) & 0xffffu), (int)(n_tiles * (unsigned)tile_bytes), 0x00020000};
+  const unsigned wave_ring = __builtin_amdgcn_readfirstlane((int)(ring_base + (unsigned)(wave * (TPS / 4) * 2048)));
   auto stage = [&](unsigned ev, int buf) __attribute__((always_inline)) {
+    const unsigned dst = wave_ring + (unsigned)(buf * TPS * 2048);
 #pragma unroll
-    for (int u = 0; u < TPS / 2; ++u) {
-      const int k = wave * (TPS / 2) + u;
-      const unsigned e = (unsigned)__builtin_amdgcn_readlane((int)ev, k >> 1);
+    for (int u = 0; u < TPS / 4; ++u) {
+      const int slot = wave * (TPS / 4) + u;
+      const unsigned e = (unsigned)__builtin_amdgcn_readlane((int)ev, slot);
       if (e >> 24) {
-        const size_t src = src_base + (size_t)(e & 0xFFFFFFu) * tile_bytes;
-        const i32x4 rsrc = {(int)(unsigned)src, (int)((src >> 32) & 0xffffu), 4096, 0x00020000};
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(
-                         (int)(ring_base + (unsigned)((buf * TPS + (k >> 1)) * 2048 + (k & 1) * 1024)))),
-                     "v"(lane16), "s"(rsrc), "s"((k & 1) * plane_stride)
-                     : "memory");
+        if (ONE_DESC) {
+          // (M0 is written in the statement that uses it; the offsets come from scalar arithmetic, the descriptor from kernel arguments)
+          const unsigned off = (e & 0xFFFFFFu) * (unsigned)tile_bytes;
+          asm volatile("s_add_u32 m0, %0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(dst), "v"(lane16), "s"(rsrc_all),
+                       "s"(off), "i"(u * 2048)
+                       : "memory", "scc");
+          asm volatile("s_add_u32 m0, %0, %4\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(dst), "v"(lane16), "s"(rsrc_all),
+                       "s"(off + (unsigned)plane_stride), "i"(u * 2048 + 1024)
+                       : "memory", "scc");
+        } else {
+          const size_t src = src_base + (size_t)(e & 0xFFFFFFu) * tile_bytes;
+          const i32x4 rsrc = {(int)(unsigned)src, (int)((src >> 32) & 0xffffu), 4096, 0x00020000};
+#pragma unroll
+          for (int pl = 0; pl < 2; ++pl)
+            asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(
+                             (int)(dst + (unsigned)(u * 2048 + pl * 1024)))),
+                         "v"(lane16), "s"(rsrc), "s"(pl * plane_stride)
+                         : "memory");
+        }
       }
     }
   };
@@ -1232,6 +1261,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     if (keep) my_list_w[out_n + __popcll(b & ((1ull << lane) - 1ull))] = (ev & 0xFFFFFFu) | (nm << 24);
     out_n += __popcll(b);
   };
+  // the A fragments of tile slot j of ring buffer buf (lane (jq, h): reference jq and jq + 32, k-half h), and the two MFMAs of a
+  // query group into one accumulator set
+  const unsigned frag_lane = (unsigned)((h * K16_TS + jq) * 16);
+  auto frags = [&](int buf, int j, f16x8& aA, f16x8& aB) __attribute__((always_inline)) {
+    const f16x8* a8 = reinterpret_cast<const f16x8*>(reinterpret_cast<const char*>(&ring[0][0][0]) + (unsigned)((buf * TPS + j) * 2048) + frag_lane);
+    aA = a8[0];
+    aB = a8[32];
+  };
+  auto group = [&](const f16x8& aA, const f16x8& aB, const f16x8& b, f32x16& cA, f32x16& cB) __attribute__((always_inline)) {
+    f32x16 z;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) z[r] = 0.0f;
+    cA = __builtin_amdgcn_mfma_f32_32x32x16_f16(aA, b, z, 0, 0, 0);
+    cB = __builtin_amdgcn_mfma_f32_32x32x16_f16(aB, b, z, 0, 0, 0);
+  };
+  auto below = [&](const f32x16& cA, const f32x16& cB, float t) __attribute__((always_inline)) {
+    return __ballot(__builtin_fminf(min16(cA), min16(cB)) < t);  // (the compare mask of the wave: scalar)
+  };
   unsigned ev_prev = 0u, ev_cur = load_entries(0), ev_nxt = load_entries(1);
   if (n_steps > 0) stage(ev_cur, 0);
   __builtin_amdgcn_s_waitcnt(0x0F70);
@@ -1242,24 +1289,40 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WPE, WPE)))
     if (s + 1 < n_steps) stage(ev_nxt, buf ^ 1);
     if (wave == 0 && s > 0) emit(ev_prev, buf ^ 1);
     unsigned mybits = 0u;
-#pragma unroll
-    for (int j = 0; j < TPS; ++j) {
-      const unsigned e = (unsigned)__builtin_amdgcn_readlane((int)ev_cur, j);
-      if ((e >> (24 + wave)) & 1u) {
-        const f16x8* a8 = reinterpret_cast<const f16x8*>(&ring[buf][j][0]) + jq;
-        const f16x8 aA = a8[h * K16_TS], aB = a8[h * K16_TS + 32];
-        // (four independent accumulators; one pair after the other -- 55 instead of 70 registers, up to eight waves per SIMD --
-        // measured 5.9 against 5.4 ms: the pass is not short of waves)
-        f32x16 c00, c01, c10, c11;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) c00[r] = c01[r] = c10[r] = c11[r] = 0.0f;
-        c00 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aA, b0[0], c00, 0, 0, 0);
-        c01 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aA, b0[1], c01, 0, 0, 0);
-        c10 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aB, b0[0], c10, 0, 0, 0);
-        c11 = __builtin_amdgcn_mfma_f32_32x32x16_f16(aB, b0[1], c11, 0, 0, 0);
-        const bool hit = __builtin_fminf(min16(c00), min16(c10)) < tA[0] || __builtin_fminf(min16(c01), min16(c11)) < tA[1];
-        if (__any(hit)) mybits |= 1u << j;
-        ++n_tested;
+    unsigned live = (unsigned)__ballot(((ev_cur >> (24 + wave)) & 1u) != 0u);  // (lanes >= TPS hold 0)
+    n_tested += (unsigned)__builtin_popcount(live);
+    if (live) {
+      int j = __builtin_ctz(live);
+      live &= live - 1u;  // (from here on: the pairs behind pair j)
+      f16x8 a0A, a0B, a1A, a1B;
+      f32x16 xA, xB, yA, yB;
+      frags(buf, j, a0A, a0B);
+      group(a0A, a0B, b0[0], xA, xB);
+      // one pair: the verdict of its group 0 (its MFMAs were issued a pair earlier), the group-0 MFMAs of the pair behind it, and --
+      // only if no lane of group 0 hit, a wave-uniform branch -- its group-1 MFMAs and their verdict, which the group-0 MFMAs of the
+      // next pair follow through the matrix pipe.  The fragment registers alternate between two calls (c: this pair's, n: the next
+      // one's) so that nothing is copied.
+      auto pair = [&](const f16x8& cA, const f16x8& cB, f16x8& nA, f16x8& nB) __attribute__((always_inline)) {
+        const bool more = live != 0u;
+        const int jn = more ? __builtin_ctz(live) : j;
+        frags(buf, jn, nA, nB);  // (the last pair of the set reads its own tile again: no branch in front of the read)
+        const unsigned long long m0 = below(xA, xB, tA[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        if (more) group(nA, nB, b0[0], xA, xB);
+        __builtin_amdgcn_sched_barrier(0);
+        unsigned long long m1 = 0ull;
+        if (m0 == 0ull) {
+          group(cA, cB, b0[1], yA, yB);
+          m1 = below(yA, yB, tA[1]);
+        }
+        if ((m0 | m1) != 0ull) mybits |= 1u << j;
+        live &= live - 1u;
+        j = jn;
+        return more;
+      };
+      for (;;) {
+        if (!pair(a0A, a0B, a1A, a1B)) break;
+        if (!pair(a1A, a1B, a0A, a0B)) break;
       }
     }
     if (lane == 0) wmask[buf][wave] = mybits;
@@ -3144,9 +3207,17 @@ extern "C" int meld_knn16_partial_filter(const void* Q16, const float* Qn, const
   const int dA = k16_dA(d, KB);
   MELD_CHECK_ARG(dA > 0 && KB >= 2, "meld_knn16_partial_filter: d = %d has no split operand layout", d);
   const unsigned n_blocks = (unsigned)ceil_div(q_count, K16_BQ);
-  hipLaunchKernelGGL((knn16_partial_filter_kernel<8, 4>), dim3(n_blocks), dim3(256), 0, S(stream), reinterpret_cast<const _Float16*>(Q16), Qn,
-                     reinterpret_cast<const _Float16*>(Rt16), scale_info, norm2_max, thr_init, step_list, step_cnt, (long long)list_stride, cnt_out,
-                     reinterpret_cast<unsigned long long*>(tested), block_order, KB, 16 + d - dA);
+  // A list holds a tile at most once and every list builder asks for list_stride >= the number of tiles: tile numbers stay below
+  // list_stride.  Where that many tiles are shorter than 4 GiB the kernel stages from one buffer descriptor over all of them (a scalar
+  // offset of 32 bits reaches every piece); otherwise from a descriptor per piece.
+  const unsigned long long rt_bytes = (unsigned long long)list_stride * (unsigned long long)KB * 4096ull;
+#define MELD_FILTER_LAUNCH(ONE)                                                                                                              \
+  hipLaunchKernelGGL((knn16_partial_filter_kernel<8, 4, ONE>), dim3(n_blocks), dim3(256), 0, S(stream), reinterpret_cast<const _Float16*>(Q16), Qn, \
+                     reinterpret_cast<const _Float16*>(Rt16), scale_info, norm2_max, thr_init, step_list, step_cnt, (long long)list_stride, cnt_out, \
+                     reinterpret_cast<unsigned long long*>(tested), block_order, KB, 16 + d - dA, (unsigned)(ONE ? list_stride : 0))
+  if (rt_bytes < (1ull << 32)) MELD_FILTER_LAUNCH(true);
+  else MELD_FILTER_LAUNCH(false);
+#undef MELD_FILTER_LAUNCH
   MELD_LAUNCH_CHECK("knn16_partial_filter_kernel");
   return MELD_OK;
 }
