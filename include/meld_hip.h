@@ -1139,6 +1139,53 @@ int meld_ranksum_scan(const uint64_t* keys_sorted, const uint64_t* payload_sorte
                       int64_t n_list, int64_t n_genes, int k, const int64_t* ncls, int64_t m, int64_t* rank2, int64_t* tie, int32_t* nnz,
                       meld_stream_t stream);
 
+/* ---- preprocessing of the counts on the device CSR (csrc/preprocess.hip; the reference's notebooks call scprep.filter.
+ *      filter_library_size / filter_rare_genes / filter_gene_set_expression, scprep.normalize.library_size_normalize and
+ *      scprep.transform.sqrt in front of meld.MELD()) -----------------------------------------------------------------------------------
+ * The operand is the CSR of the cells-by-genes matrix: rowptr[n_rows + 1] int64, col[nnz] int32 in [0, n_cols), val[nnz] fp32
+ * (val_f32 = 1, widened exactly) or fp64; stored zeros allowed, rows of any length, nnz beyond 2^31.  All arithmetic is fp64, no
+ * floating-point atomics: every output is a function of the operands alone.  A column index outside [0, n_cols) is skipped by every
+ * kernel before it addresses anything.
+ *
+ * meld_prep_row_stats: per row i over its COUNTED entries -- all of them, or with col_mask (uint8 [n_cols]) those with
+ *   col_mask[col] != 0 --: sum[i] = the sum of v, abs_sum[i] = the sum of |v|, count[i] (int32) = the number with v > cutoff.
+ *   Order of the sums: a wave per row; the counted entries numbered 0, 1, 2 ... in storage order, lane l adds the entries l, l + 64,
+ *   ... in that order, then a fixed tree over the 64 lanes: a function of the number of counted entries alone, so the masked sums
+ *   of a row have the bits of the plain sums of the row meld_prep_select_fill leaves when it drops the same columns.
+ * meld_prep_col_counts: count[c] (int32 [n_cols], ZEROED BY THE CALLER) += the number of entries of column c with v > cutoff in
+ *   the rows with row_keep[row] != 0 (uint8 [n_rows]; NULL: every row).  A workgroup walks a contiguous range of rows, counts into a
+ *   panel of MELD_PREP_PANEL_COLS int32 counters in LDS (integer LDS atomics) and adds the non-zero ones to count with integer
+ *   global atomics; a matrix of more columns takes one launch per panel, entries outside the panel are skipped.
+ * meld_prep_select_count / meld_prep_select_fill: the matrix of the rows rows[n_keep] (int32, ascending: new row -> old row) and the
+ *   columns with col_map[c] >= 0 (int32 [n_cols]: old column -> new column, the kept columns numbered ascending; NULL: every
+ *   column keeps its index).  count: counts[i] (int32 [n_keep]) = the kept entries of new row i; the caller scans them
+ *   (meld_exclusive_scan_i32_i64) into out_rowptr[n_keep + 1].  fill: out_col / out_val [out_rowptr[n_keep]] in storage order (a
+ *   stored zero that survives the column selection stays stored; a row never writes past out_rowptr[i + 1]).  The value, in this
+ *   order of operations:  w = scale ? (v / scale[i]) * rescale : v  (scale fp64 [n_keep] or NULL; a row with scale[i] == 0 keeps v,
+ *   rescale still multiplies: sklearn's normalize), then out_val = f(w) for transform MELD_PREP_IDENTITY w, _SQRT sqrt(w), _LOG
+ *   log(w + 1), _LOG2 log2(w + 1), _LOG10 log10(w + 1), _ARCSINH asinh(w / cofactor).  out_val_norm (NULL: not wanted) receives w.
+ *
+ * Each entry returns -1 before any launch, naming itself, for a NULL required pointer, val_f32 outside {0, 1}, n_rows, n_cols or
+ * n_keep outside [1, 2^31), a transform outside [0, 5], a cofactor <= 0 with MELD_PREP_ARCSINH. */
+#define MELD_PREP_PANEL_COLS 32768
+#define MELD_PREP_IDENTITY 0
+#define MELD_PREP_SQRT 1
+#define MELD_PREP_LOG 2
+#define MELD_PREP_LOG2 3
+#define MELD_PREP_LOG10 4
+#define MELD_PREP_ARCSINH 5
+int meld_prep_panel_cols(void);
+int meld_prep_row_stats(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t n_rows, int64_t n_cols,
+                        const uint8_t* col_mask, double cutoff, double* sum, double* abs_sum, int32_t* count, meld_stream_t stream);
+int meld_prep_col_counts(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t n_rows, int64_t n_cols,
+                         const uint8_t* row_keep, double cutoff, int32_t* count, meld_stream_t stream);
+int meld_prep_select_count(const int64_t* rowptr, const int32_t* col, int64_t n_rows, int64_t n_cols, const int32_t* rows,
+                           int64_t n_keep, const int32_t* col_map, int32_t* counts, meld_stream_t stream);
+int meld_prep_select_fill(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t n_rows, int64_t n_cols,
+                          const int32_t* rows, int64_t n_keep, const int32_t* col_map, const double* scale, double rescale,
+                          int transform, double cofactor, const int64_t* out_rowptr, int32_t* out_col, double* out_val,
+                          double* out_val_norm, meld_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

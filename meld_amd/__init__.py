@@ -21,6 +21,7 @@ __all__ = [
     "KMeans",
     "LeidenRecord",
     "rank_sum_test",
+    "preprocess",
     "Benchmarker",
     "utils",
     "filter",
@@ -46,6 +47,10 @@ def __getattr__(name):
         from .diffexp import rank_sum_test
 
         return rank_sum_test
+    if name == "preprocess":  # filter, normalise and transform the counts on the device CSR (the reference's notebooks: scprep)
+        import importlib
+
+        return importlib.import_module(".preprocess", __name__)
     if name == "Benchmarker":  # host-side helper of the reference package (meld/benchmark.py), lazy like the above
         from .benchmark import Benchmarker
 

@@ -223,6 +223,11 @@ SIGNATURES = {
     "meld_ranksum_gather": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _ptr, _ptr, _i64, _i64, _ptr, _i64, _i32, _ptr, _ptr, _ptr]),
     "meld_sort_pairs_u64_u64": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _i32, _i32, _ptr, _sz, _ptr]),
     "meld_ranksum_scan": (_i32, [_ptr, _ptr, _ptr, _ptr, _i64, _i64, _i32, _ptr, _i64, _ptr, _ptr, _ptr, _ptr]),
+    "meld_prep_panel_cols": (_i32, []),
+    "meld_prep_row_stats": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _ptr, _f64, _ptr, _ptr, _ptr, _ptr]),
+    "meld_prep_col_counts": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _ptr, _f64, _ptr, _ptr]),
+    "meld_prep_select_count": (_i32, [_ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr]),
+    "meld_prep_select_fill": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _ptr, _i64, _ptr, _ptr, _f64, _i32, _f64, _ptr, _ptr, _ptr, _ptr, _ptr]),
 }
 
 

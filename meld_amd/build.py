@@ -10,7 +10,7 @@ import sys
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
-SOURCES = ["api.hip", "knn.hip", "knn16.hip", "refine.hip", "assemble.hip", "spmm.hip", "spmm_tiled.hip", "reorder.hip", "kmeans.hip", "kmeans_wide.hip", "labels.hip", "sharded.hip", "frame.hip", "csr_dense.hip", "metric_knn.hip", "extend.hip", "subspace.hip", "components.hip", "diffuse.hip", "geodesic.hip", "landmark.hip", "mds.hip", "louvain.hip", "leiden.hip", "ranksum.hip"]
+SOURCES = ["api.hip", "knn.hip", "knn16.hip", "refine.hip", "assemble.hip", "spmm.hip", "spmm_tiled.hip", "reorder.hip", "kmeans.hip", "kmeans_wide.hip", "labels.hip", "sharded.hip", "frame.hip", "csr_dense.hip", "metric_knn.hip", "extend.hip", "subspace.hip", "components.hip", "diffuse.hip", "geodesic.hip", "landmark.hip", "mds.hip", "louvain.hip", "leiden.hip", "ranksum.hip", "preprocess.hip"]
 OUT = os.path.join(_HERE, "libmeld_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result"]
 # per-file additions.  knn16.hip: the minima over MFMA accumulators (tile bounds, seeds) are fmin chains on values the compiler
@@ -19,7 +19,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-res
 # finite on the host, paddings are +inf by construction, never inf - inf -- and the graph is bit-identical with and without.
 # louvain.hip: the score of a move is stated operation by operation (tests/louvain_reference.py evaluates it with numpy); a fused
 # multiply-add would round it differently.  leiden.hip: the same for the scores of the refinement (tests/leiden_reference.py).
-FILE_FLAGS = {"knn16.hip": ["-fno-honor-nans"], "louvain.hip": ["-ffp-contract=off"], "leiden.hip": ["-ffp-contract=off"]}
+# preprocess.hip: the same for the value map (v / s) * r and log(w + 1) (tests/preprocess_reference.py); no fast-math either.
+FILE_FLAGS = {"knn16.hip": ["-fno-honor-nans"], "louvain.hip": ["-ffp-contract=off"], "leiden.hip": ["-ffp-contract=off"],
+              "preprocess.hip": ["-ffp-contract=off"]}
 
 
 def _hipcc():

@@ -190,6 +190,15 @@ class GraphEstimator(object):
             return self
         from . import sparse as _sparse
 
+        if isinstance(X, _sparse.DeviceCSR):
+            # a matrix that is on the device already (meld_amd.preprocess): taken as it is, like a device tensor
+            if self.X is not X:
+                self.graph = None
+            self.X = X
+            if self.graph is None:
+                self._log("Building graph on {} samples and {} features.".format(X.shape[0], X.shape[1]))
+                self.graph = self._build_timed(X, **kwargs)
+            return self
         if _sparse.is_sparse_input(X):
             # sparse cell-by-gene input: one canonical CSR matrix on the host, never densified there (meld_amd/sparse.py)
             A = _sparse.to_host_csr(X)

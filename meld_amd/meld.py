@@ -471,6 +471,9 @@ class MELD(GraphEstimator):
             frame = isinstance(X, pd.DataFrame)
             st.columns = X.columns if frame else None
             st.index = X.index if frame else None
+            if isinstance(X, _sparse.DeviceCSR):  # (a preprocessed matrix carries the labels of the frame it was made from)
+                st.columns = None if X.gene_names is None else pd.Index(X.gene_names)
+                st.index = None if X.cell_index is None else pd.Index(X.cell_index)
         return self
 
     def impute(self, genes=None, t=3):

@@ -59,8 +59,9 @@ def _pandas_sparse(X):
 
 def is_sparse_input(X):
     """True for the inputs this front end takes: scipy.sparse, all-sparse DataFrames, AnnData-like objects with a sparse
-    ``.X`` and device tensors of layout ``torch.sparse_csr``."""
-    if _is_torch_csr(X):
+    ``.X``, device tensors of layout ``torch.sparse_csr`` and a ``DeviceCSR`` (a matrix that is on the device already, the
+    output of ``meld_amd.preprocess`` for one)."""
+    if _is_torch_csr(X) or isinstance(X, DeviceCSR):
         return True
     X = _unwrap(X)
     return _is_torch_csr(X) or _scipy_sparse().issparse(X) or _pandas_sparse(X)
@@ -97,6 +98,9 @@ class DeviceCSR:
         self.nnz = int(col.shape[0])
         self._plan = None
         self._T = None
+        # the labels of the rows and columns where the input carried them (meld_amd/preprocess.py keeps them through its filters)
+        self.cell_index = None
+        self.gene_names = None
 
     @property
     def device(self):
@@ -104,7 +108,10 @@ class DeviceCSR:
 
     @classmethod
     def from_input(cls, X, device="cuda"):
-        """Upload a host sparse input (or adopt a device ``torch.sparse_csr`` tensor, no PCIe), check its indices and values."""
+        """Upload a host sparse input (or adopt a device ``torch.sparse_csr`` tensor, no PCIe), check its indices and values.
+        A ``DeviceCSR`` is returned as it is."""
+        if isinstance(X, cls):
+            return X
         X = _unwrap(X)
         if _is_torch_csr(X):
             if X.dim() != 2:
@@ -243,6 +250,16 @@ class DeviceCSR:
 
     def to_dense(self):
         return self.rows_to_dense(0, self.shape[0])
+
+    def to_scipy(self):
+        """The matrix on the host: a ``scipy.sparse.csr_matrix`` of the same structure (stored zeros included) and value dtype."""
+        indptr = self.rowptr.cpu().numpy()
+        indices = self.col.cpu().numpy()
+        if self.nnz > np.iinfo(np.int32).max:
+            indices = indices.astype(np.int64)
+        else:
+            indptr = indptr.astype(np.int32)
+        return _scipy_sparse().csr_matrix((self.val.cpu().numpy(), indices, indptr), shape=self.shape)
 
 
 def truncated_svd_project(A, k, seed=42, return_model=False):
