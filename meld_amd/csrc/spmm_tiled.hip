@@ -1121,7 +1121,9 @@ __global__ __launch_bounds__(THREADS) void pt_fill_kernel(const int64_t* __restr
   const int in_base = n_in_chunks << 6;
   const int total = in_base + s_eoff[63];  // entries of the wave's stream
   uint64_t hsum = 0;
-  for (int a0 = 0; a0 < total; a0 += FILL_CAP) {  // slot ranges that fit the LDS image (one, as a rule)
+  // slot ranges that fit the LDS image (one, as a rule).  A wave without a stream -- its rows hold nothing but lower in-block
+  // entries -- still takes the first pass: those entries owe their half of the symmetry sum (span = 0: nothing is stored)
+  for (int a0 = 0; a0 < total || a0 == 0; a0 += FILL_CAP) {
     const int span = min(FILL_CAP, total - a0);
     for (int i = tid; i < span; i += THREADS) {  // padding pattern: value 0, column slot 0, row 0, no flush
       s_val[i] = 0.0;

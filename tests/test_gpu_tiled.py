@@ -8,6 +8,8 @@ import pytest
 import torch
 from scipy import sparse
 
+from tests import tiled_reference as tr
+
 pytestmark = pytest.mark.gpu
 
 
@@ -187,57 +189,16 @@ def test_tiled_layout_holds_every_nonzero_once_and_is_reproducible():
     pt = G.ops.pt_layout(G)
     assert pt is not None and G.info["spmm_fold"] is True
     t = {k: v.cpu().numpy() for k, v in pt["tensors"].items()}
-    nw, rmax, cp, tmax = C.c_int(), C.c_int(), C.c_int(), C.c_int()
-    get_lib().meld_pt_geometry(C.byref(nw), C.byref(rmax), C.byref(cp), C.byref(tmax))
-    nw, cp, rmax = nw.value, cp.value, rmax.value
-    slots, segw, segrows, padcap = rmax // nw, 64, 2 * (nw + 1), 64
-    rowptr = G.rowptr.cpu().numpy()
-    nb = pt["nb"]
-    blk_row = t["blk_row"]
-    assert blk_row[0] == 0 and blk_row[nb] == G.n_rows and np.all(np.diff(blk_row) >= 0) and np.diff(blk_row).max() <= rmax
-    pidx = t["pidx"].view(np.uint32)
-
-    def row_of(slot):  # inverse of the kernel's row_slot()
-        return (slot % slots) * nw + slot // slots
-
-    rows, cols, vals = [], [], []
-    n_pairs = 0
-    for b in range(nb):
-        segp = t["seg"][b * segrows * segw : (b + 1) * segrows * segw].reshape(segrows, segw)
-        T, e0, r0 = int(t["blk_ntile"][b]), int(rowptr[blk_row[b]]), int(blk_row[b])
-        assert segp[segrows - 1, 2] == r0 and segp[segrows - 1, 4] == T
-        lst = t["list_cols"][e0 : e0 + int(t["blk_ndist"][b])]
-        assert np.all(np.diff(lst) > 0)  # sorted distinct columns
-        base_b = e0 + b * nw * padcap
-        for w in range(nw):
-            hdr = int(np.uint32(segp[w, 62]))
-            n_in, soff = hdr & 0xFFFF, int(segp[w, 63])
-            eoff = segp[nw + 1 + w]
-            sb = base_b + soff
-            # IN pairs: whole chunks, padded with (0, 0) entries
-            ix, v = pidx[sb : sb + 64 * n_in], t["pval"][sb : sb + 64 * n_in]
-            keep = v != 0
-            ri, rj = row_of((ix[keep] >> 20).astype(np.int64)), row_of(((ix[keep] >> 4) & 0xFFF).astype(np.int64))
-            assert keep.sum() == eoff[62] and np.all(ri < rj) and np.all(ri % nw == w)
-            rows += [r0 + ri, r0 + rj]
-            cols += [r0 + rj, r0 + ri]
-            vals += [v[keep], v[keep]]
-            n_pairs += int(keep.sum())
-            # OUT entries: dense, tile by tile
-            for j in range(T):
-                s, e = sb + 64 * n_in + int(eoff[j]), sb + 64 * n_in + int(eoff[j + 1] if j + 1 < T else eoff[63])
-                ix = pidx[s:e]
-                cs = ((ix >> 4) & 0xFFF).astype(np.int64)
-                assert np.all(cs >> 10 == (j & 3))
-                rl = row_of((ix >> 20).astype(np.int64))
-                assert np.all(rl % nw == w)
-                rows.append(r0 + rl)
-                cols.append(lst[int(segp[nw, j]) * cp + (cs & (cp - 1))])  # row nw of seg: list chunk of the j-th processed tile
-                vals.append(t["pval"][s:e])
-    M = sparse.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(G.n_rows, G.N))
-    ref = sparse.csr_matrix((G.val.cpu().numpy(), G.col.cpu().numpy(), rowptr), shape=(G.n_rows, G.N))
-    assert M.nnz == ref.nnz and abs(M - ref).max() == 0.0
-    assert n_pairs > 0.1 * ref.nnz  # the fold is doing something on a kNN graph in locality order
+    geo = [C.c_int() for _ in range(4)]
+    get_lib().meld_pt_geometry(*(C.byref(g) for g in geo))
+    nw = geo[0].value
+    rowptr, col, val = G.rowptr.cpu().numpy(), G.col.cpu().numpy(), G.val.cpu().numpy()
+    # the decoder of tests/tiled_reference.py: plan, headers, column lists, every nonzero decoded back exactly once and bit for bit
+    # (OUT entries through the column lists, IN pairs mirrored), padding, flags, descriptors, offsets, the fp32 copy
+    assert tr.check_layout(t, rowptr, col, val, G.row_begin, tuple(g.value for g in geo)) == []
+    segrows = 2 * (nw + 1)
+    n_pairs = int(t["seg"].reshape(pt["nb"], segrows, 64)[:, nw + 1 :segrows - 1, 62].sum())
+    assert n_pairs > 0.1 * G.nnz  # the fold is doing something on a kNN graph in locality order
     # reproducible to rounding
     x = torch.rand(G.N, 2, dtype=torch.float64, device="cuda")
     ys = []
