@@ -125,7 +125,7 @@ def build(force=False, verbose=True):
     objdir = os.path.join(_HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     headers = [os.path.join(CSRC, "common.hpp"), os.path.join(CSRC, "k16_rows.hpp"), os.path.join(CSRC, "csr_wave_stream.hpp"),
-               os.path.join(_HERE, "..", "include", "meld_hip.h")]
+               os.path.join(CSRC, "label_rows.hpp"), os.path.join(_HERE, "..", "include", "meld_hip.h")]
     procs = []
     objs = []
     for src in SOURCES:

@@ -51,6 +51,7 @@ import pandas as pd
 import torch
 
 from . import utils
+from ._device_ops import stream
 
 __all__ = ["VertexFrequencyCluster"]
 
@@ -70,7 +71,7 @@ def _lloyd_step(Y, C, lab, scratch):
     k = C.shape[0]
     nb = scratch["nb"]
     check(lib.meld_kmeans_assign(ptr(Y), n, d, ptr(C), k, ptr(lab), ptr(scratch["sum"]), ptr(scratch["cnt"]), ptr(scratch["in"]),
-                                 nb, torch.cuda.current_stream().cuda_stream), "meld_kmeans_assign")
+                                 nb, stream()), "meld_kmeans_assign")
     sums = scratch["sum"].view(nb, k, d).sum(0)  # fixed-order reduction of the per-workgroup partials
     cnt = scratch["cnt"].view(nb, k).sum(0)
     newC = torch.where(cnt[:, None] > 0, sums / cnt.clamp(min=1.0)[:, None], C)

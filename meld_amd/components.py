@@ -11,6 +11,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from ._device_ops import scan_i32, stream
 from ._graph_steps import require_unsharded, rounds_until_unchanged
 from ._lib import check, get_lib, ptr
 
@@ -63,16 +64,10 @@ def selection_index(ind, N):
     return ind
 
 
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
 def connected_components_device(G, recompute=False, max_rounds=None):
     """``(n_components, labels)`` of ``G``: ``labels`` an int32 device tensor ``[N]`` in the caller's cell order, components
     numbered by their smallest cell.  Kept on the graph (with the sizes, and ``G.components_info``); RuntimeError when
     ``max_rounds`` rounds (default ``default_max_rounds(N)``) do not reach the fixed point."""
-    from .graph import _scan_i32
-
     require_unsharded(G, "connected components are")
     kept = getattr(G, "_components", None)
     if kept is not None and not recompute:
@@ -81,7 +76,7 @@ def connected_components_device(G, recompute=False, max_rounds=None):
     max_rounds = default_max_rounds(N) if max_rounds is None else int(max_rounds)
     if max_rounds < 1:
         raise ValueError("max_rounds must be at least 1, got {}".format(max_rounds))
-    lib, st = get_lib(), _stream()
+    lib, st = get_lib(), stream()
     parent = torch.arange(N, dtype=torch.int32, device=dev)
     changed = torch.zeros(1, dtype=torch.int32, device=dev)
     def one_round(_):
@@ -95,7 +90,7 @@ def connected_components_device(G, recompute=False, max_rounds=None):
     count = torch.empty(N, dtype=torch.int32, device=dev)
     flags = torch.empty(N, dtype=torch.int32, device=dev)
     check(lib.meld_cc_minima(ptr(parent), ptr(G.perm), N, ptr(min_orig), ptr(count), ptr(flags), st), "meld_cc_minima")
-    rank = _scan_i32(lib, flags, st)
+    rank = scan_i32(flags)
     n = int(rank[N].item())
     labels = torch.empty(N, dtype=torch.int32, device=dev)
     sizes = torch.empty(n, dtype=torch.int64, device=dev)
@@ -108,7 +103,7 @@ def connected_components_device(G, recompute=False, max_rounds=None):
 
 def subgraph(G, ind):
     """The graph induced by the cells ``ind`` (see ``DeviceGraph.subgraph``)."""
-    from .graph import DeviceGraph, _scan_i32
+    from .graph import DeviceGraph
 
     require_unsharded(G, "a subgraph is")
     N, dev = G.N, G.rowptr.device
@@ -127,10 +122,10 @@ def subgraph(G, ind):
     new_index[rows] = torch.arange(k, dtype=torch.int32, device=dev)
     sub_perm = pos[rows]  # device row t of the result is cell sub_perm[t] of the result
 
-    lib, st = get_lib(), _stream()
+    lib, st = get_lib(), stream()
     counts = torch.empty(k, dtype=torch.int32, device=dev)
     check(lib.meld_subgraph_count(ptr(G.rowptr), ptr(G.col), ptr(new_index), N, ptr(counts), st), "meld_subgraph_count")
-    rowptr = _scan_i32(lib, counts, st)
+    rowptr = scan_i32(counts)
     nnz = int(rowptr[k].item())
     col = torch.empty(nnz, dtype=torch.int32, device=dev)
     val = torch.empty(nnz, dtype=torch.float64, device=dev)

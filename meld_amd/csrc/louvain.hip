@@ -17,13 +17,9 @@
 // vertex only if b < a; a vertex of a larger community may move to b < a in even rounds and to b > a in odd ones (two neighbours
 // cannot swap, a pair cannot chase each other).  own_i = w_a + A_ii, so that sum_i own_i = sum_c in_c of the labels READ.
 //
-// Move kernel.  G = 16 or 64 lanes per row (a kNN row of 8 to 14 entries fills a 16-lane group; four rows per wave), 256 threads per
-// workgroup.  The row is taken 4 G entries at a time (four per lane: label, tot and size of their columns' communities gathered
-// once), and every such chunk meets ALL entries of the row, which pass through LDS in tiles of 4 G (label, value): one broadcast read
-// per four comparisons, sum += (label_j == label_i) ? v_j : 0 in storage order.  So every entry knows the whole weight of its label,
-// whatever the row's length (a row longer than a tile takes several trips; the work is quadratic in the length), duplicates of a label agree and
-// the argmax over the lanes (a xor butterfly on (g, id)) needs no leader.  The groups of a wave have rows of their own lengths; a
-// group's lanes share their control flow and their LDS rows, so a wave-level fence orders its LDS traffic.  Per workgroup the rows'
+// Move kernel.  louvain_move_kernel<G> is the row pass of label_rows.hpp (G = 16 or 64 lanes per row; the scheme is stated there)
+// with lv_move_op: the label of an entry is c_j, -1 for the diagonal; the first chunk's trips leave w_a and A_ii; every row goes on;
+// an entry is scored by g(b) under the allowed test above (size and tot of its community gathered once).  Per workgroup the rows'
 // own_i and mover flags go through LDS and are added by one thread in row order; louvain_reduce_kernel adds the workgroups'
 // partials: thread t takes the partials t, t + 256, ... in order, then a fixed tree.  fp64 throughout, no atomics, nothing shared
 // between workgroups: every output is a function of the operands alone, the same bits every run.
@@ -33,17 +29,11 @@
 // ascending order, then a xor butterfly); a segment of one element is stored by its own lane.  Leaves tot, size and the smallest
 // member of every present label, zeros / -1 for the others.
 // As compiled (-Rpass-analysis=kernel-resource-usage): no kernel of this file touches private memory (tests/test_louvain_host.py).
-#include "common.hpp"
-
-#include <limits.h>
+#include "label_rows.hpp"
 
 namespace meld {
 
-constexpr int LV_THREADS = 256;
-constexpr int LV_SHORT = 16;   // lanes per row where the rows are short
-constexpr int LV_LONG = 64;    // lanes per row otherwise
-constexpr int LV_U = 4;        // entries of the row a lane holds at a time: a trip through LDS serves G * LV_U of them
-constexpr double LV_SHORT_MEAN = 64.0;  // mean entries per row up to which LV_SHORT is chosen: what one trip of 16 lanes holds
+constexpr double LV_SHORT_MEAN = 64.0;  // mean entries per row up to which LR_SHORT is chosen: what one trip of 16 lanes holds
 
 // the label of entry i of a row of `len` entries: -1 for padding and for the diagonal entry (never a candidate), and for a label
 // outside [0, n) (labels become addresses of tot and size)
@@ -56,103 +46,72 @@ __device__ __forceinline__ int lv_entry_label(const int* __restrict__ col, const
   return (unsigned long long)l < (unsigned long long)n ? l : -1;
 }
 
+// what the move rule adds to the row pass (label_rows.hpp): the row r of community a
+struct lv_move_op {
+  const int* __restrict__ col;
+  const int* __restrict__ labels;
+  const double* __restrict__ tot;
+  const int* __restrict__ size;
+  long long n;
+  double two_m;
+  int odd;
+  long long r;  // the row and its community
+  int a;
+  long long rs = 0, len = 0;  // set for a live row
+  int size_a = 0;
+  double gk = 0.0;
+  double wa = 0.0, self = 0.0;  // w_a and A_ii
+  label_best best{-__builtin_inf(), INT_MAX};
+  __device__ __forceinline__ int label(long long i) const { return lv_entry_label(col, labels, rs, len, r, n, i); }
+  __device__ __forceinline__ void meet(int lj, double vj) {
+    wa += (lj == a) ? vj : 0.0;
+    self += (lj < 0) ? vj : 0.0;  // (padding carries 0)
+  }
+  __device__ __forceinline__ bool go_on() const { return true; }
+  __device__ __forceinline__ void score(int b, double w) {
+    if (b >= 0 && b != a) {
+      const int size_b = size[b];
+      const bool allowed = size_a == 1 ? (size_b > 1 || b < a) : (odd ? b > a : b < a);
+      const double gb = w * two_m - gk * tot[b];  // (built with -ffp-contract=off: three roundings)
+      if (allowed) best.offer(gb, b);
+    }
+  }
+};
+
 template <int G>
-__global__ __launch_bounds__(LV_THREADS) void louvain_move_kernel(const long long* __restrict__ rowptr, const int* __restrict__ col,
+__global__ __launch_bounds__(LR_THREADS) void louvain_move_kernel(const long long* __restrict__ rowptr, const int* __restrict__ col,
                                                                   const double* __restrict__ val, long long n,
                                                                   const int* __restrict__ label, const double* __restrict__ k,
                                                                   const double* __restrict__ tot, const int* __restrict__ size,
                                                                   double two_m, double gamma, int odd, int* __restrict__ new_label,
                                                                   double* __restrict__ own, int* __restrict__ moved,
                                                                   double* __restrict__ part_sum, int* __restrict__ part_moved) {
-  constexpr int ROWS = LV_THREADS / G;
-  constexpr int TILE = G * LV_U;
-  __shared__ int s_lab[ROWS][TILE];
-  __shared__ double s_val[ROWS][TILE];
+  constexpr int ROWS = LR_THREADS / G;
+  __shared__ label_tiles<G> s_tiles;
   __shared__ double s_own[ROWS];
   __shared__ int s_mov[ROWS];
   const int g = threadIdx.x / G;
   const int sub = threadIdx.x % G;
   const long long r = (long long)blockIdx.x * ROWS + g;
-  int a = r < n ? label[r] : -1;
+  const int a = r < n ? label[r] : -1;
   const bool live = (unsigned long long)a < (unsigned long long)n;  // (a label is an address of tot and size: outside [0, n) the row stays)
-  double best_g = -__builtin_inf();
-  int best_b = INT_MAX;
-  double wa = 0.0, self = 0.0, gk = 0.0;
-  int size_a = 0;
+  lv_move_op op{col, label, tot, size, n, two_m, odd, r, a};
   if (live) {
-    const long long rs = rowptr[r];
-    const long long len = rowptr[r + 1] - rs;
-    gk = gamma * k[r];
-    size_a = size[a];
-    for (long long i0 = 0; i0 < len; i0 += TILE) {
-      int li[LV_U];
-      double vi[LV_U], sum[LV_U];
-#pragma unroll
-      for (int u = 0; u < LV_U; ++u) {
-        const long long i = i0 + sub + G * u;
-        li[u] = lv_entry_label(col, label, rs, len, r, n, i);
-        vi[u] = i < len ? val[rs + i] : 0.0;
-        sum[u] = 0.0;
-      }
-      const bool first = i0 == 0;
-      for (long long j0 = 0; j0 < len; j0 += TILE) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // (one wave: the loads of the last trip precede these stores)
-#pragma unroll
-        for (int u = 0; u < LV_U; ++u) {
-          if (j0 == i0) {  // (uniform over the group: the tile is the chunk its lanes hold)
-            s_lab[g][sub + G * u] = li[u];
-            s_val[g][sub + G * u] = vi[u];
-          } else {
-            const long long j = j0 + sub + G * u;
-            s_lab[g][sub + G * u] = lv_entry_label(col, label, rs, len, r, n, j);
-            s_val[g][sub + G * u] = j < len ? val[rs + j] : 0.0;
-          }
-        }
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");  // (one wave: its LDS stores precede its loads)
-        const int jn = (int)min((long long)TILE, len - j0);
-        for (int jj = 0; jj < jn; ++jj) {
-          const int lj = s_lab[g][jj];  // (one address for the group: a broadcast)
-          const double vj = s_val[g][jj];
-#pragma unroll
-          for (int u = 0; u < LV_U; ++u) sum[u] += (lj == li[u]) ? vj : 0.0;  // (x + 0 == x: the label's entries in storage order)
-          if (first) {                                                        // (the first chunk meets every entry of the row once)
-            wa += (lj == a) ? vj : 0.0;
-            self += (lj < 0) ? vj : 0.0;  // (padding carries 0)
-          }
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < LV_U; ++u) {
-        const int b = li[u];
-        if (b >= 0 && b != a) {
-          const int size_b = size[b];
-          const bool allowed = size_a == 1 ? (size_b > 1 || b < a) : (odd ? b > a : b < a);
-          const double gb = sum[u] * two_m - gk * tot[b];  // (built with -ffp-contract=off: three roundings)
-          if (allowed && (gb > best_g || (gb == best_g && b < best_b))) {
-            best_g = gb;
-            best_b = b;
-          }
-        }
-      }
-    }
+    op.rs = rowptr[r];
+    op.len = rowptr[r + 1] - op.rs;
+    op.gk = gamma * k[r];
+    op.size_a = size[a];
+    label_row_pass<G>(s_tiles, val, op);
   }
-#pragma unroll
-  for (int off = G / 2; off > 0; off >>= 1) {
-    const double og = __shfl_xor(best_g, off, 64);
-    const int ob = __shfl_xor(best_b, off, 64);
-    if (og > best_g || (og == best_g && ob < best_b)) {
-      best_g = og;
-      best_b = ob;
-    }
-  }
+  op.best.over_lanes<G>();
   if (sub == 0) {
     double mine = 0.0;
     int mv = 0;
     if (live) {
-      const double ga = wa * two_m - gk * (tot[a] - k[r]);
-      mv = (best_b != INT_MAX && best_g > ga) ? 1 : 0;
-      mine = wa + self;
-      new_label[r] = mv ? best_b : a;
+      const double ga = op.wa * two_m - op.gk * (tot[a] - k[r]);
+      mv = (op.best.id != INT_MAX && op.best.score > ga) ? 1 : 0;
+      mine = op.wa + op.self;
+      new_label[r] = mv ? op.best.id : a;
       own[r] = mine;
       moved[r] = mv;
     } else if (r < n) {
@@ -178,20 +137,20 @@ __global__ __launch_bounds__(LV_THREADS) void louvain_move_kernel(const long lon
 }
 
 // stats[0] = the sum of part_sum, stats[1] = the sum of part_moved (as a double: exact below 2^53)
-__global__ __launch_bounds__(LV_THREADS) void louvain_reduce_kernel(const double* __restrict__ part_sum,
+__global__ __launch_bounds__(LR_THREADS) void louvain_reduce_kernel(const double* __restrict__ part_sum,
                                                                     const int* __restrict__ part_moved, long long n_parts,
                                                                     double* __restrict__ stats) {
-  __shared__ double s_sum[LV_THREADS];
-  __shared__ double s_mov[LV_THREADS];
+  __shared__ double s_sum[LR_THREADS];
+  __shared__ double s_mov[LR_THREADS];
   double s = 0.0, m = 0.0;
-  for (long long p = threadIdx.x; p < n_parts; p += LV_THREADS) {
+  for (long long p = threadIdx.x; p < n_parts; p += LR_THREADS) {
     s += part_sum[p];
     m += (double)part_moved[p];
   }
   s_sum[threadIdx.x] = s;
   s_mov[threadIdx.x] = m;
   __syncthreads();
-  for (int off = LV_THREADS / 2; off > 0; off >>= 1) {
+  for (int off = LR_THREADS / 2; off > 0; off >>= 1) {
     if ((int)threadIdx.x < off) {
       s_sum[threadIdx.x] += s_sum[threadIdx.x + off];
       s_mov[threadIdx.x] += s_mov[threadIdx.x + off];
@@ -206,11 +165,11 @@ __global__ __launch_bounds__(LV_THREADS) void louvain_reduce_kernel(const double
 
 __device__ __forceinline__ int lv_key_label(const unsigned long long* __restrict__ keys, long long e) { return (int)(keys[e] >> 32); }
 
-__global__ __launch_bounds__(LV_THREADS) void louvain_totals_kernel(const unsigned long long* __restrict__ keys,
+__global__ __launch_bounds__(LR_THREADS) void louvain_totals_kernel(const unsigned long long* __restrict__ keys,
                                                                     const double* __restrict__ vals, long long n, long long n_labels,
                                                                     double* __restrict__ tot, int* __restrict__ size,
                                                                     int* __restrict__ minm) {
-  const long long t = (long long)blockIdx.x * LV_THREADS + threadIdx.x;
+  const long long t = (long long)blockIdx.x * LR_THREADS + threadIdx.x;
   const int lane = threadIdx.x & 63;
   const bool in = t < n;
   const int lab = in ? lv_key_label(keys, t) : -1;
@@ -251,19 +210,19 @@ __global__ __launch_bounds__(LV_THREADS) void louvain_totals_kernel(const unsign
 }
 
 // flags[v] = 1 where v is the smallest member of its community
-__global__ __launch_bounds__(LV_THREADS) void louvain_heads_kernel(const int* __restrict__ label, const int* __restrict__ minm,
+__global__ __launch_bounds__(LR_THREADS) void louvain_heads_kernel(const int* __restrict__ label, const int* __restrict__ minm,
                                                                    long long n, int* __restrict__ flags) {
-  const long long v = (long long)blockIdx.x * LV_THREADS + threadIdx.x;
+  const long long v = (long long)blockIdx.x * LR_THREADS + threadIdx.x;
   if (v >= n) return;
   const int b = label[v];
   flags[v] = ((unsigned long long)b < (unsigned long long)n && minm[b] == (int)v) ? 1 : 0;
 }
 
-__global__ __launch_bounds__(LV_THREADS) void louvain_renumber_kernel(const int* __restrict__ label, const int* __restrict__ minm,
+__global__ __launch_bounds__(LR_THREADS) void louvain_renumber_kernel(const int* __restrict__ label, const int* __restrict__ minm,
                                                                       const long long* __restrict__ rank,
                                                                       const int* __restrict__ size, long long n,
                                                                       int* __restrict__ out, long long* __restrict__ sizes) {
-  const long long v = (long long)blockIdx.x * LV_THREADS + threadIdx.x;
+  const long long v = (long long)blockIdx.x * LR_THREADS + threadIdx.x;
   if (v >= n) return;
   const int b = label[v];
   if ((unsigned long long)b >= (unsigned long long)n) return;
@@ -276,10 +235,10 @@ __global__ __launch_bounds__(LV_THREADS) void louvain_renumber_kernel(const int*
 
 constexpr int LV_ROW = 16;  // lanes per row of the two streaming kernels below
 
-__global__ __launch_bounds__(LV_THREADS) void louvain_keys_kernel(const long long* __restrict__ rowptr, const int* __restrict__ col,
+__global__ __launch_bounds__(LR_THREADS) void louvain_keys_kernel(const long long* __restrict__ rowptr, const int* __restrict__ col,
                                                                   long long n, const int* __restrict__ label,
                                                                   unsigned long long* __restrict__ keys) {
-  const long long t = (long long)blockIdx.x * LV_THREADS + threadIdx.x;
+  const long long t = (long long)blockIdx.x * LR_THREADS + threadIdx.x;
   const long long r = t / LV_ROW;
   const int sub = (int)(t % LV_ROW);
   if (r >= n) return;
@@ -290,11 +249,11 @@ __global__ __launch_bounds__(LV_THREADS) void louvain_keys_kernel(const long lon
 
 // own[i] = sum_{j : c_j = c_i} A_ij (the diagonal included), k[i] = sum_j A_ij: lane s of the row's 16 adds the entries s, s + 16, ...
 // in order, then a xor butterfly
-__global__ __launch_bounds__(LV_THREADS) void modularity_terms_kernel(const long long* __restrict__ rowptr, const int* __restrict__ col,
+__global__ __launch_bounds__(LR_THREADS) void modularity_terms_kernel(const long long* __restrict__ rowptr, const int* __restrict__ col,
                                                                       const double* __restrict__ val, long long n,
                                                                       const int* __restrict__ label, double* __restrict__ own,
                                                                       double* __restrict__ k) {
-  const long long t = (long long)blockIdx.x * LV_THREADS + threadIdx.x;
+  const long long t = (long long)blockIdx.x * LR_THREADS + threadIdx.x;
   const long long r = t / LV_ROW;
   const int sub = (int)(t % LV_ROW);
   double in = 0.0, all = 0.0;
@@ -322,15 +281,15 @@ __global__ __launch_bounds__(LV_THREADS) void modularity_terms_kernel(const long
 
 using namespace meld;
 
-static inline unsigned lv_blocks(int64_t work) { return (unsigned)ceil_div(work, LV_THREADS); }
+static inline unsigned lv_blocks(int64_t work) { return (unsigned)ceil_div(work, LR_THREADS); }
 
 extern "C" int meld_louvain_lanes(int64_t n, int64_t nnz) {
-  return (n > 0 && (double)nnz <= LV_SHORT_MEAN * (double)n) ? LV_SHORT : LV_LONG;
+  return (n > 0 && (double)nnz <= LV_SHORT_MEAN * (double)n) ? LR_SHORT : LR_LONG;
 }
 
 extern "C" int64_t meld_louvain_move_blocks(int64_t n, int lanes) {
-  if (n <= 0 || (lanes != LV_SHORT && lanes != LV_LONG)) return 0;
-  return ceil_div(n, LV_THREADS / lanes);
+  if (n <= 0 || (lanes != LR_SHORT && lanes != LR_LONG)) return 0;
+  return ceil_div(n, LR_THREADS / lanes);
 }
 
 extern "C" int meld_louvain_move(const int64_t* rowptr, const int32_t* col, const double* val, int64_t n, const int32_t* label,
@@ -340,22 +299,22 @@ extern "C" int meld_louvain_move(const int64_t* rowptr, const int32_t* col, cons
   MELD_CHECK_ARG(rowptr && label && k && tot && size && new_label && own && moved && part_sum && part_moved && stats,
                  "meld_louvain_move: rowptr, label, k, tot, size, new_label, own, moved, part_sum, part_moved and stats are required");
   MELD_CHECK_ARG(n >= 1 && n < (1ll << 31), "meld_louvain_move: n=%lld outside [1, 2^31)", (long long)n);
-  MELD_CHECK_ARG(lanes == LV_SHORT || lanes == LV_LONG, "meld_louvain_move: lanes=%d (%d or %d per row)", lanes, LV_SHORT, LV_LONG);
+  MELD_CHECK_ARG(lanes == LR_SHORT || lanes == LR_LONG, "meld_louvain_move: lanes=%d (%d or %d per row)", lanes, LR_SHORT, LR_LONG);
   MELD_CHECK_ARG(round >= 0, "meld_louvain_move: round=%d is negative", round);
   MELD_CHECK_ARG(two_m >= 0.0 && two_m < __builtin_inf() && gamma > 0.0 && gamma < __builtin_inf(),
                  "meld_louvain_move: two_m=%g, gamma=%g (a finite two_m >= 0 and a finite gamma > 0)", two_m, gamma);
   MELD_CHECK_ARG(new_label != label, "meld_louvain_move: new_label is label (a round reads labels other rows would have written)");
   const long long* rp = reinterpret_cast<const long long*>(rowptr);
   const long long blocks = meld_louvain_move_blocks(n, lanes);
-  if (lanes == LV_SHORT) {
-    louvain_move_kernel<LV_SHORT><<<(unsigned)blocks, LV_THREADS, 0, S(stream)>>>(rp, col, val, n, label, k, tot, size, two_m, gamma,
+  if (lanes == LR_SHORT) {
+    louvain_move_kernel<LR_SHORT><<<(unsigned)blocks, LR_THREADS, 0, S(stream)>>>(rp, col, val, n, label, k, tot, size, two_m, gamma,
                                                                                   round & 1, new_label, own, moved, part_sum, part_moved);
   } else {
-    louvain_move_kernel<LV_LONG><<<(unsigned)blocks, LV_THREADS, 0, S(stream)>>>(rp, col, val, n, label, k, tot, size, two_m, gamma,
+    louvain_move_kernel<LR_LONG><<<(unsigned)blocks, LR_THREADS, 0, S(stream)>>>(rp, col, val, n, label, k, tot, size, two_m, gamma,
                                                                                  round & 1, new_label, own, moved, part_sum, part_moved);
   }
   MELD_LAUNCH_CHECK("louvain_move_kernel");
-  louvain_reduce_kernel<<<1, LV_THREADS, 0, S(stream)>>>(part_sum, part_moved, blocks, stats);
+  louvain_reduce_kernel<<<1, LR_THREADS, 0, S(stream)>>>(part_sum, part_moved, blocks, stats);
   MELD_LAUNCH_CHECK("louvain_reduce_kernel");
   return MELD_OK;
 }
@@ -368,7 +327,7 @@ extern "C" int meld_louvain_totals(const uint64_t* keys_sorted, const double* va
   MELD_HIP_CALL(hipMemsetAsync(tot, 0, (size_t)n_labels * sizeof(double), S(stream)));
   MELD_HIP_CALL(hipMemsetAsync(size, 0, (size_t)n_labels * 4, S(stream)));
   MELD_HIP_CALL(hipMemsetAsync(minm, 0xff, (size_t)n_labels * 4, S(stream)));
-  louvain_totals_kernel<<<lv_blocks(n), LV_THREADS, 0, S(stream)>>>(reinterpret_cast<const unsigned long long*>(keys_sorted), vals_sorted, n,
+  louvain_totals_kernel<<<lv_blocks(n), LR_THREADS, 0, S(stream)>>>(reinterpret_cast<const unsigned long long*>(keys_sorted), vals_sorted, n,
                                                                     n_labels, tot, size, minm);
   MELD_LAUNCH_CHECK("louvain_totals_kernel");
   return MELD_OK;
@@ -377,7 +336,7 @@ extern "C" int meld_louvain_totals(const uint64_t* keys_sorted, const double* va
 extern "C" int meld_louvain_heads(const int32_t* label, const int32_t* minm, int64_t n, int32_t* flags, meld_stream_t stream) {
   MELD_CHECK_ARG(label && minm && flags, "meld_louvain_heads: label, minm and flags are required");
   MELD_CHECK_ARG(n >= 1 && n < (1ll << 31), "meld_louvain_heads: n=%lld outside [1, 2^31)", (long long)n);
-  louvain_heads_kernel<<<lv_blocks(n), LV_THREADS, 0, S(stream)>>>(label, minm, n, flags);
+  louvain_heads_kernel<<<lv_blocks(n), LR_THREADS, 0, S(stream)>>>(label, minm, n, flags);
   MELD_LAUNCH_CHECK("louvain_heads_kernel");
   return MELD_OK;
 }
@@ -386,7 +345,7 @@ extern "C" int meld_louvain_renumber(const int32_t* label, const int32_t* minm, 
                                      int32_t* out, int64_t* sizes, meld_stream_t stream) {
   MELD_CHECK_ARG(label && minm && rank && size && out && sizes, "meld_louvain_renumber: label, minm, rank, size, out and sizes are required");
   MELD_CHECK_ARG(n >= 1 && n < (1ll << 31), "meld_louvain_renumber: n=%lld outside [1, 2^31)", (long long)n);
-  louvain_renumber_kernel<<<lv_blocks(n), LV_THREADS, 0, S(stream)>>>(label, minm, reinterpret_cast<const long long*>(rank), size, n, out,
+  louvain_renumber_kernel<<<lv_blocks(n), LR_THREADS, 0, S(stream)>>>(label, minm, reinterpret_cast<const long long*>(rank), size, n, out,
                                                                       reinterpret_cast<long long*>(sizes));
   MELD_LAUNCH_CHECK("louvain_renumber_kernel");
   return MELD_OK;
@@ -396,7 +355,7 @@ extern "C" int meld_louvain_contract_keys(const int64_t* rowptr, const int32_t* 
                                           meld_stream_t stream) {
   MELD_CHECK_ARG(rowptr && col && label && keys, "meld_louvain_contract_keys: rowptr, col, label and keys are required");
   MELD_CHECK_ARG(n >= 1 && n < (1ll << 31), "meld_louvain_contract_keys: n=%lld outside [1, 2^31)", (long long)n);
-  louvain_keys_kernel<<<lv_blocks(n * LV_ROW), LV_THREADS, 0, S(stream)>>>(reinterpret_cast<const long long*>(rowptr), col, n, label,
+  louvain_keys_kernel<<<lv_blocks(n * LV_ROW), LR_THREADS, 0, S(stream)>>>(reinterpret_cast<const long long*>(rowptr), col, n, label,
                                                                            reinterpret_cast<unsigned long long*>(keys));
   MELD_LAUNCH_CHECK("louvain_keys_kernel");
   return MELD_OK;
@@ -406,7 +365,7 @@ extern "C" int meld_modularity_terms(const int64_t* rowptr, const int32_t* col, 
                                      double* own, double* k, meld_stream_t stream) {
   MELD_CHECK_ARG(rowptr && label && own && k, "meld_modularity_terms: rowptr, label, own and k are required");
   MELD_CHECK_ARG(n >= 1 && n < (1ll << 31), "meld_modularity_terms: n=%lld outside [1, 2^31)", (long long)n);
-  modularity_terms_kernel<<<lv_blocks(n * LV_ROW), LV_THREADS, 0, S(stream)>>>(reinterpret_cast<const long long*>(rowptr), col, val, n,
+  modularity_terms_kernel<<<lv_blocks(n * LV_ROW), LR_THREADS, 0, S(stream)>>>(reinterpret_cast<const long long*>(rowptr), col, val, n,
                                                                                label, own, k);
   MELD_LAUNCH_CHECK("modularity_terms_kernel");
   return MELD_OK;

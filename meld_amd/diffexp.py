@@ -215,8 +215,8 @@ def rank_sums_device(data, codes, k, force_long=False, timings=None):
 
     import torch
 
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
-    from .sparse import _stream
 
     lib = get_lib()
     k = int(k)
@@ -247,7 +247,7 @@ def rank_sums_device(data, codes, k, force_long=False, timings=None):
     valid = (code >= 0) & (code < k)
     n_c = torch.bincount(code[valid].to(torch.int64), minlength=k).to(torch.int64)
     m = int(n_c.sum())
-    st = _stream()
+    st = stream()
     rank2 = torch.empty(G, k, dtype=torch.int64, device=dev)
     tie = torch.empty(G, dtype=torch.int64, device=dev)
     nnz = torch.empty(G, k, dtype=torch.int32, device=dev)

@@ -121,6 +121,7 @@ def diffuse_device(G, F, t=1, device_order=False):
     import torch
 
     from . import filter as _filter
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
 
     t = check_t(t)
@@ -139,7 +140,7 @@ def diffuse_device(G, F, t=1, device_order=False):
     second = (X if ours else torch.empty_like(X)) if t >= 2 else None
     bufs = (first, second)
     lib = get_lib()
-    st = torch.cuda.current_stream().cuda_stream
+    st = stream()
     rowptr, col, val = csr_operands(G, G.val)
     esz = X.element_size()
     for c0, w in panels(p):  # all t steps of one panel before the next

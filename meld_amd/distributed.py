@@ -29,6 +29,7 @@ import pandas as pd
 import torch
 import torch.distributed as dist
 
+from ._device_ops import stream
 from .graph import DeviceGraph, metric_front_end, resolve_graph_params
 from .graph_plan import plan_graph, plan_reduction
 from .mnn import build_mnn_graph
@@ -99,7 +100,7 @@ class Comm:
                 if ok:
                     try:
                         # one all-reduce and one in-place all-gather through the new communicator before it is trusted with the filter
-                        st = torch.cuda.current_stream().cuda_stream
+                        st = stream()
                         probe = torch.ones(4, dtype=torch.float64, device="cuda")
                         check(lib.meld_rccl_all_reduce_sum_f64(h, C.c_void_p(probe.data_ptr()), 4, st), "meld_rccl_all_reduce_sum_f64")
                         full = torch.full((self.world, 2), -1.0, dtype=torch.float64, device="cuda")

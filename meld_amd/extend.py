@@ -27,15 +27,12 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from ._device_ops import stream
 from ._lib import check, get_lib, ptr
 
 __all__ = ["ExtensionState", "attach_extension_state", "kernel_to_data_device", "apply_transitions"]
 
 _EPS = float(np.finfo(float).eps)
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class ExtensionState(SimpleNamespace):
@@ -212,7 +209,7 @@ def extend_rows(keys, half_vals, row_begin, n_rows, n_cols):
     tb = int(lib.meld_extend_rows_temp_bytes(n, n_rows))
     tmp = torch.empty(tb, dtype=torch.uint8, device=dev)
     check(lib.meld_extend_rows(ptr(keys), ptr(half_vals), n, int(row_begin), int(n_rows), int(n_cols), ptr(rowptr), ptr(col), ptr(val), ptr(rowsum),
-                               ptr(tmp), tb, _stream()), "meld_extend_rows")
+                               ptr(tmp), tb, stream()), "meld_extend_rows")
     return rowptr, col[:n], val[:n], rowsum
 
 
@@ -225,7 +222,7 @@ def apply_transitions(csr, F, colmap=None):
     out = torch.zeros(M, p, dtype=torch.float64, device=F.device)
     if int(col.shape[0]) == 0 or p == 0:
         return out
-    check(get_lib().meld_extend_apply(ptr(rowptr), ptr(col), ptr(val), ptr(rowsum), M, ptr(F), int(F.shape[0]), p, ptr(colmap), ptr(out), _stream()),
+    check(get_lib().meld_extend_apply(ptr(rowptr), ptr(col), ptr(val), ptr(rowsum), M, ptr(F), int(F.shape[0]), p, ptr(colmap), ptr(out), stream()),
           "meld_extend_apply")
     return out
 

@@ -20,6 +20,7 @@ from ._options import opt
 import numpy as np
 import torch
 
+from ._device_ops import stream
 from ._lib import check, get_lib, ptr
 from .graph import HipOps, _EventSpan
 
@@ -60,7 +61,7 @@ class IndicatorSignal:
         scale = None if self.scale is None else torch.from_numpy(self.scale).to(device)
         out = torch.empty((int(n_pad), self.n_columns), dtype=torch.float64, device=device)
         check(get_lib().meld_indicator_signal(ptr(codes.contiguous()), ptr(scale), ptr(perm), self.shape[0], int(n_pad), self.n_columns,
-                                              ptr(out), torch.cuda.current_stream().cuda_stream), "meld_indicator_signal")
+                                              ptr(out), stream()), "meld_indicator_signal")
         return out
 
     def to_device(self, device):
@@ -72,10 +73,6 @@ class IndicatorSignal:
             vals = torch.from_numpy(self.scale).to(device)[codes]
         out[torch.arange(self.shape[0], device=device), codes] = vals
         return out
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class _PinnedPool:
@@ -556,7 +553,7 @@ def _to_caller_order(r, graph):
     if perm is not None:
         r_orig = torch.empty_like(r)
         if r.dim() == 2 and r.is_cuda and r.dtype == torch.float64 and r.is_contiguous():
-            check(get_lib().meld_scatter_rows_f64(ptr(r), ptr(perm), int(r.shape[0]), int(r.shape[1]), ptr(r_orig), _stream()), "meld_scatter_rows_f64")
+            check(get_lib().meld_scatter_rows_f64(ptr(r), ptr(perm), int(r.shape[0]), int(r.shape[1]), ptr(r_orig), stream()), "meld_scatter_rows_f64")
         else:
             r_orig[..., perm, :] = r
         r = r_orig

@@ -110,6 +110,7 @@ def edge_lengths_device(G, distance=None):
     ``"affinity"``); NotImplementedError, naming the case, where ``"data"`` has no cells to measure (``data_refusal``)."""
     import torch
 
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
 
     distance = default_distance(G) if distance is None else check_distance(distance)
@@ -132,7 +133,7 @@ def edge_lengths_device(G, distance=None):
         L = torch.empty(G.nnz, dtype=torch.float64, device=G.val.device)
         if G.nnz:
             check(get_lib().meld_edge_lengths_l2(ptr(G.rowptr), ptr(G.col), G.N, ptr(X), int(X.shape[1]), int(X.shape[1]), ptr(L),
-                                                 torch.cuda.current_stream().cuda_stream), "meld_edge_lengths_l2")
+                                                 stream()), "meld_edge_lengths_l2")
     bad = int((~(torch.isfinite(L) & (L >= 0))).sum())
     if bad:
         raise ValueError("{} of the {} edge lengths under distance={!r} are not finite and >= 0{}".format(
@@ -152,6 +153,7 @@ def shortest_path_device(G, sources, distance=None, min_only=False, device_order
     import torch
 
     from . import filter as _filter
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
 
     require_unsharded(G, "shortest paths are")
@@ -172,7 +174,7 @@ def shortest_path_device(G, sources, distance=None, min_only=False, device_order
         D[rows, 0 if min_only else torch.arange(p, device=dev)] = 0.0
     if p and N:
         lib = get_lib()
-        st = torch.cuda.current_stream().cuda_stream
+        st = stream()
         rowptr, col, L = csr_operands(G, L)
         # the rounds of a panel take turns between its columns of D and of `other`, a block of the same shape (the same columns of
         # both: the ranges the entry compares never meet); the round that lowers nothing leaves both equal, so D holds the result

@@ -19,6 +19,8 @@ from types import SimpleNamespace
 import numpy as np
 import torch
 
+from ._device_ops import coo_merge, csr_from_keys, scan_i32, sort_pairs, stream
+from ._device_ops import stream as _stream  # (the name the contract tests import from here)
 from ._lib import check, get_lib, ptr
 from .knn_plan import SearchOptions, bucket_route, plan_knn_search, search_nprod, sphere_layout
 
@@ -58,10 +60,6 @@ def event_times_ms():
     for name, a, b, meta in EVENTS["pairs"]:
         out.setdefault(name, []).append(a.elapsed_time(b))
     return out
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def default_ksel(knn):
@@ -727,15 +725,6 @@ def _radius_factor(decay, thresh):
     return 1.0 if math.isinf(decay) else float((-math.log(thresh)) ** (1.0 / decay))
 
 
-def _scan_i32(lib, x, st):
-    n = x.shape[0]
-    out = torch.empty(n + 1, dtype=torch.int64, device=x.device)
-    tb = lib.meld_scan_temp_bytes(n)
-    tmp = torch.empty(tb, dtype=torch.uint8, device=x.device)
-    check(lib.meld_exclusive_scan_i32_i64(ptr(x), ptr(out), n, ptr(tmp), tb, st), "meld_exclusive_scan_i32_i64")
-    return out
-
-
 class HipOps:
     """Local (per-GPU) stages of the path as calls into libmeld_hip.so.  The single-GPU builder
     and the row-sharded driver (``meld_amd.distributed``) compose the same stages; only the
@@ -762,7 +751,7 @@ class HipOps:
         out = torch.empty(3, d, dtype=torch.float64, device=X.device)
         tb = self.lib.meld_col_stats_temp_bytes(d)
         tmp = torch.empty(tb, dtype=torch.uint8, device=X.device)
-        check(self.lib.meld_col_stats_f64(ptr(X), N, d, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(tmp), tb, _stream()), "meld_col_stats_f64")
+        check(self.lib.meld_col_stats_f64(ptr(X), N, d, ptr(out[0]), ptr(out[1]), ptr(out[2]), ptr(tmp), tb, stream()), "meld_col_stats_f64")
         return out[0], out[1], out[2]
 
     def frame_axes_async(self, X, col_stats):
@@ -776,7 +765,7 @@ class HipOps:
         N, d = int(X.shape[0]), int(X.shape[1])
         if col_stats is None or d > int(lib.meld_frame_max_dims()) or not plan_knn_search(lib, N, d, 0, N, 1, 2, options=self).frame:
             return None
-        st = _stream()
+        st = stream()
         mean = col_stats[0] / N
         cov = torch.zeros(d, d, dtype=torch.float64, device=X.device)
         check(lib.meld_cov_sample_f64(ptr(X), N, d, ptr(mean), max(1, N // 32768), ptr(cov), st), "meld_cov_sample_f64")
@@ -804,7 +793,7 @@ class HipOps:
         block; any frame is valid, the graph is the same).  Distances are those of ``X`` to
         rounding (V is orthonormal to 1e-15): the search only nominates candidates, their distances are evaluated in fp64 on
         ``X`` itself.  The d x d eigenproblem is solved on the host (one read-back of d x d numbers)."""
-        lib, st = self.lib, _stream()
+        lib, st = self.lib, stream()
         N, d = int(X.shape[0]), int(X.shape[1])
         if axes is not None and (comm is None or getattr(comm, "world", 1) == 1):
             # (the axes were started before the ordering: frame_axes_async)
@@ -998,7 +987,7 @@ class HipOps:
 
     def _candidates_f32(self, a, plan, ksel, mean, norm2, nmax):
         """fp32 operands on v_mfma_f32_32x32x2_f32 (knn.hip)."""
-        lib, st, dev, X, N, d = self.lib, _stream(), a.X.device, a.X, a.N, a.d
+        lib, st, dev, X, N, d = self.lib, stream(), a.X.device, a.X, a.N, a.d
         KP = lib.meld_knn_padded_dim(d)
         if KP < 0:
             check(KP, "meld_knn_padded_dim")
@@ -1051,7 +1040,7 @@ class HipOps:
         """The split-fp16 operands, in the cells' principal frame where the plan asks for it and the data carry one: everything up
         to the candidate lists works on X_s, refinement and the exact sweeps on X.  Returns the plan as it stands after the frame's
         test, the operands and the largest norm the error bounds speak of."""
-        lib, st, dev, X, N, d = self.lib, _stream(), a.X.device, a.X, a.N, a.d
+        lib, st, dev, X, N, d = self.lib, stream(), a.X.device, a.X, a.N, a.d
         KB, TS, BQ = lib.meld_knn16_kblocks(d), lib.meld_knn16_tile_refs(), lib.meld_knn16_block_queries()
         o = SimpleNamespace(X_s=X, mean_s=mean, KB=KB, BQ=BQ, n_tiles=(a.NR + TS - 1) // TS, q_pad=((a.q_count + BQ - 1) // BQ) * BQ)
         if plan.frame:
@@ -1084,7 +1073,7 @@ class HipOps:
 
     def _start_thresholds(self, a, plan, o, c, rfac):
         """Start thresholds of the first pass (scaled units) instead of +inf, or None."""
-        lib, st, dev = self.lib, _stream(), a.X.device
+        lib, st, dev = self.lib, stream(), a.X.device
         if plan.seed == "bandwidth":
             # every row's radius is known: the thresholds start there, with the row's search-error allowance on top
             rad = (a.bw_fixed[a.q_begin : a.q_begin + a.q_count] * float(a.bw_scale)).clamp_(min=float(np.finfo(float).eps)) * _radius_factor(a.decay, a.thresh)
@@ -1110,7 +1099,7 @@ class HipOps:
         without pruning."""
         if not plan.prune:
             return None, None, None, None
-        lib, st, dev, N, d = self.lib, _stream(), a.X.device, a.N, a.d
+        lib, st, dev, N, d = self.lib, stream(), a.X.device, a.N, a.d
         X_s, mean_s, n_tiles, n_blocks = o.X_s, o.mean_s, o.n_tiles, o.q_pad // o.BQ
         spheres_ready = getattr(o, "spheres", None) is not None  # (meld_knn16_prepare_fused left them there)
         tmpb = o.spheres if spheres_ready else torch.empty(lib.meld_knn16_bounds_temp_bytes(N, d, a.q_count), dtype=torch.uint8, device=dev)
@@ -1162,7 +1151,7 @@ class HipOps:
     def _search16(self, a, plan, o, c, ksel, seeds, rfac, lists):
         """The first pass: the partial filter where the plan has one (the search then stages whole tiles for the quarter of the
         pairs that survive), then the search itself, over ``plan.main_slices`` slices of the references."""
-        lib, st, dev, d, q_count, q_pad, cap = self.lib, _stream(), a.X.device, a.d, a.q_count, o.q_pad, c.cap
+        lib, st, dev, d, q_count, q_pad, cap = self.lib, stream(), a.X.device, a.d, a.q_count, o.q_pad, c.cap
         lb2, step_list, step_cnt, block_order = lists
         q0 = 0 if a.cross else a.q_begin
         tiles_b = c.tiles_done
@@ -1211,7 +1200,7 @@ class HipOps:
         the full hi/lo split (a few % of the rows) where the plan has that stage; then ONE read-back of the scalars the host
         wants here (each one is an idle gap of the GPU of ~50 us: nothing is queued behind it): rows still flagged, kept
         entries, (wave, tile) pairs the first pass computed."""
-        lib, st, dev, q_count = self.lib, _stream(), a.X.device, a.q_count
+        lib, st, dev, q_count = self.lib, stream(), a.X.device, a.q_count
         r = SimpleNamespace(plan=c.plan, cands=c)
         max_rank = 0 if a.knn_max is None else int(a.knn_max) + 1  # (self counted, as graphtools counts it)
         r.bw = torch.empty(q_count, dtype=torch.float64, device=dev)
@@ -1252,7 +1241,7 @@ class HipOps:
         if stage2:
             self._stage2(a, c, r, ksel, n_flag, max_rank)
         c.research = None
-        r.keep_off = _scan_i32(lib, r.keep_cnt, st)
+        r.keep_off = scan_i32(r.keep_cnt)
         td, p = c.tiles_done, c.plan
         heads = [n_flag[0].to(torch.int64), r.keep_off[q_count]] + ([td[0], td[2] if p.two_pass else td[1], td[1]] if td is not None else [])
         heads_h = torch.stack(heads).tolist()
@@ -1268,7 +1257,7 @@ class HipOps:
 
     def _stage2(self, a, c, r, ksel, n_flag, max_rank):
         """The flagged rows searched again with the full hi/lo split; only what that cannot certify either goes to the exact sweep."""
-        lib, st, dev, d, cap, o = self.lib, _stream(), a.X.device, a.d, c.cap, c.research
+        lib, st, dev, d, cap, o = self.lib, stream(), a.X.device, a.d, c.cap, c.research
         n_flag_h = r.n_flag
         rows2 = torch.sort(r.flag_rows[:n_flag_h]).values.contiguous()
         if r.buckets is not None:  # (fused row pass: the first stage stored no kernel values; these rows' are stored at their local row)
@@ -1317,7 +1306,7 @@ class HipOps:
     def _exact_sweep(self, a, r, count_rows_ge):
         """Exact sweep of the rows the candidate lists could not certify (their bandwidth recomputed where a list missed one of
         the knn nearest cells, knn_max applied to the swept rows), and the count of rows with at least ``count_rows_ge`` cells."""
-        lib, st, dev, q_count, n_flag_h = self.lib, _stream(), a.X.device, a.q_count, r.n_flag
+        lib, st, dev, q_count, n_flag_h = self.lib, stream(), a.X.device, a.q_count, r.n_flag
         knn_chk = a.knn if a.bw_fixed is None else 2**31 - 1  # (a given bandwidth is not verified against the neighbour count)
         s = SimpleNamespace(n_rebandwidth=0, fb_total=0, fb_off=None, fb_col=None, fb_val=None, fb_cnt=None, rows_at_least=None)
         if n_flag_h > 0:
@@ -1347,7 +1336,7 @@ class HipOps:
                     raise NotImplementedError(
                         "degenerate neighbourhoods: the exact sweep could not settle the bandwidth of {} rows".format(int((fb_cnt < 0).sum())))
                 s.n_rebandwidth = int(bad.shape[0])
-            fb_off = _scan_i32(lib, fb_cnt, st)
+            fb_off = scan_i32(fb_cnt)
             fb_total = int(fb_off[n_flag_h].item())
             # (a radius that covers most of the data -- small decay with a small thresh -- makes the graph effectively dense: say so
             # instead of failing inside an allocation; the reference's scipy matrices would be as large)
@@ -1371,7 +1360,7 @@ class HipOps:
                 keep = keep[torch.argsort(rows_e[keep], stable=True)]
                 fb_col, fb_val = fb_col[keep].contiguous(), fb_val[keep].contiguous()
                 fb_cnt = torch.clamp(fb_cnt, max=int(a.knn_max))
-                fb_off = _scan_i32(lib, fb_cnt, st)
+                fb_off = scan_i32(fb_cnt)
                 fb_total = int(fb_off[n_flag_h].item())
             s.fb_total, s.fb_off, s.fb_col, s.fb_val, s.fb_cnt = fb_total, fb_off, fb_col, fb_val, fb_cnt
         a.tm.stop("radius_exact")
@@ -1390,7 +1379,7 @@ class HipOps:
         None; with the degrees (``anisotropy`` given), val is the kernel with the anisotropy applied.  On the fused route
         (``plan.fused_rows``) the refinement has filled the buckets with the complete rows already: the rows of the second stage and
         the swept entries follow (meld_coo_emit_scatter_listed); buckets that cannot be finished then return (None, None, None)."""
-        lib, st, dev, q_count, n_flag_h, c = self.lib, _stream(), a.X.device, a.q_count, r.n_flag, r.cands
+        lib, st, dev, q_count, n_flag_h, c = self.lib, stream(), a.X.device, a.q_count, r.n_flag, r.cands
         M = r.m_main + s.fb_total
         assembled = None
         # (plan.fused_rows: the refinement filled the buckets with the complete rows; meld_amd.metric_knn hands in rows of its own)
@@ -1445,18 +1434,7 @@ class HipOps:
         return keys, vals, assembled
 
     # ---- A4: (K + K^T)/2 rows [row_begin, row_begin + n_rows) from unsorted COO ---------------------
-    def sort_pairs(self, keys, vals, N):
-        lib, st = self.lib, _stream()
-        n = int(keys.shape[0])
-        keys2 = torch.empty_like(keys)
-        vals2 = torch.empty_like(vals)
-        if n == 0:
-            return keys2, vals2
-        tb = lib.meld_sort_temp_bytes(n)
-        tmp = torch.empty(tb, dtype=torch.uint8, device=keys.device)
-        end_bit = 32 + max(1, int(N - 1).bit_length())
-        check(lib.meld_sort_pairs_u64_f64(ptr(keys), ptr(keys2), ptr(vals), ptr(vals2), n, end_bit, ptr(tmp), tb, st), "meld_sort_pairs_u64_f64")
-        return keys2, vals2
+    sort_pairs = staticmethod(sort_pairs)  # (part of the ops interface: distributed.py calls it on the object)
 
     def partition_remote(self, keys, vals, rows_per_rank, world, rank, cap):
         """Row-sharded build: the entries owed to the other ranks in a fixed-capacity send buffer [world, 2, cap] (keys |
@@ -1466,7 +1444,7 @@ class HipOps:
         counts = torch.empty(world, dtype=torch.int32, device=dev)
         send = torch.empty(world * 2 * cap, dtype=torch.int64, device=dev)
         check(self.lib.meld_coo_partition_remote(ptr(keys), ptr(vals), int(keys.shape[0]), int(rows_per_rank), int(world), int(rank),
-                                                 int(cap), ptr(counts), ptr(send), _stream()), "meld_coo_partition_remote")
+                                                 int(cap), ptr(counts), ptr(send), stream()), "meld_coo_partition_remote")
         return send, counts
 
     def _finish_buckets(self, cursor, tcol, tval, n_rows, sums_diag=None, symm=(0, 0.0), anisotropy=None):
@@ -1476,7 +1454,7 @@ class HipOps:
         the buckets hold ALL rows of the graph): the row sums come out of the merge, and the compaction writes
         K_ij / (ksum_i ksum_j)^a and sums the degrees (``last_degrees``) -- the CSR is written once, with the bits of
         ``meld_csr_compact_rows_sums`` + ``meld_csr_anisotropy_degrees``."""
-        lib, st, dev = self.lib, _stream(), cursor.device
+        lib, st, dev = self.lib, stream(), cursor.device
         i32 = dict(dtype=torch.int32, device=dev)
         ucnt = torch.empty(n_rows, **i32)
         flags = torch.empty(1, **i32)
@@ -1487,7 +1465,7 @@ class HipOps:
                                                     float(sums_diag), ptr(sums), st), "meld_csr_rows_sort_merge_sums")
         else:
             check(lib.meld_csr_rows_sort_merge(ptr(cursor), n_rows, ptr(tcol), ptr(tval), ptr(ucnt), ptr(flags), int(symm[0]), float(symm[1]), st), "meld_csr_rows_sort_merge")
-        rowptr = _scan_i32(lib, ucnt, st)
+        rowptr = scan_i32(ucnt)
         nnz, flag = (int(v) for v in torch.stack([rowptr[n_rows], flags[0].to(torch.int64)]).tolist())  # (one read-back)
         if flag != 0:
             return None
@@ -1516,7 +1494,7 @@ class HipOps:
         ``MELD_ASSEMBLE=sort`` -- by a global radix sort + reduce-by-key.  ``foreign``: the input may hold entries of
         rows outside the slice (the fixed-capacity exchange of the sharded build: other ranks' rows, sentinel keys);
         the bucket path ignores them, the sort path drops them first."""
-        lib, st, dev = self.lib, _stream(), keys.device
+        lib, st, dev = self.lib, stream(), keys.device
         n = int(keys.shape[0])
         B = int(lib.meld_csr_bucket_slots())
         # the buckets cost 12 B x B slots per row whatever the degree (3 KB per row: 3 GB at 1M rows): above a quarter of
@@ -1562,16 +1540,8 @@ class HipOps:
             ukeys, uvals = keys2[first][keep].contiguous(), v[keep].contiguous()
             nnz = int(ukeys.shape[0])
         else:
-            tb = lib.meld_merge_temp_bytes(max(n, 1))
-            tmp = torch.empty(tb, dtype=torch.uint8, device=dev)
-            n_unique = torch.zeros(1, dtype=torch.int64, device=dev)
-            ukeys = torch.empty_like(keys2)
-            uvals = torch.empty_like(vals2)
-            check(lib.meld_coo_merge(ptr(keys2), ptr(vals2), n, ptr(ukeys), ptr(uvals), ptr(n_unique), ptr(tmp), tb, st), "meld_coo_merge")
-            nnz = int(n_unique.item())
-        rowptr = torch.empty(n_rows + 1, dtype=torch.int64, device=dev)
-        col = torch.empty(nnz, dtype=torch.int32, device=dev)
-        check(lib.meld_csr_from_keys(ptr(ukeys), nnz, row_begin, n_rows, ptr(rowptr), ptr(col), st), "meld_csr_from_keys")
+            ukeys, uvals, nnz = coo_merge(keys2, vals2)
+        rowptr, col = csr_from_keys(ukeys, nnz, row_begin, n_rows)
         return rowptr, col, uvals[:nnz].clone()
 
     def gather_rows(self, X, perm):
@@ -1579,22 +1549,22 @@ class HipOps:
         X = X.contiguous()
         perm = perm.to(torch.int64).contiguous()
         out = torch.empty((int(perm.shape[0]), int(X.shape[1])), dtype=torch.float64, device=X.device)
-        check(self.lib.meld_gather_rows_f64(ptr(X), ptr(perm), int(perm.shape[0]), int(X.shape[1]), ptr(out), _stream()), "meld_gather_rows_f64")
+        check(self.lib.meld_gather_rows_f64(ptr(X), ptr(perm), int(perm.shape[0]), int(X.shape[1]), ptr(out), stream()), "meld_gather_rows_f64")
         return out
 
     def row_sums(self, rowptr, val, n_rows, diag):
         out = torch.empty(n_rows, dtype=torch.float64, device=rowptr.device)
-        check(self.lib.meld_csr_row_sums(ptr(rowptr), ptr(val), n_rows, float(diag), ptr(out), _stream()), "meld_csr_row_sums")
+        check(self.lib.meld_csr_row_sums(ptr(rowptr), ptr(val), n_rows, float(diag), ptr(out), stream()), "meld_csr_row_sums")
         return out
 
     def anisotropy(self, rowptr, col, val, n_rows, ksum_all, row_off, a):
-        check(self.lib.meld_csr_anisotropy(ptr(rowptr), ptr(col), ptr(val), n_rows, ptr(ksum_all), row_off, float(a), _stream()), "meld_csr_anisotropy")
+        check(self.lib.meld_csr_anisotropy(ptr(rowptr), ptr(col), ptr(val), n_rows, ptr(ksum_all), row_off, float(a), stream()), "meld_csr_anisotropy")
 
     def anisotropy_degrees(self, rowptr, col, val, n_rows, ksum_all, row_off, a):
         """``anisotropy`` and the row sums of its result in one pass (``meld_csr_anisotropy_degrees``: the same bits as
         ``row_sums(..., 0.0)`` afterwards)."""
         dw = torch.empty(n_rows, dtype=torch.float64, device=val.device)
-        check(self.lib.meld_csr_anisotropy_degrees(ptr(rowptr), ptr(col), ptr(val), n_rows, ptr(ksum_all), row_off, float(a), ptr(dw), _stream()),
+        check(self.lib.meld_csr_anisotropy_degrees(ptr(rowptr), ptr(col), ptr(val), n_rows, ptr(ksum_all), row_off, float(a), ptr(dw), stream()),
               "meld_csr_anisotropy_degrees")
         return dw
 
@@ -1703,7 +1673,7 @@ class HipOps:
         for symmetric in ((1, 0) if fold else (0,)):
             with _EventSpan("pt_build", N=G.N, nnz=G.nnz):
                 check(lib.meld_pt_build(ptr(G.rowptr), ptr(G.col), ptr(G.val), G.n_rows, G.n_pad, G.row_begin, symmetric,
-                                        C.byref(lay), ptr(codes), ptr(status), _stream()), "meld_pt_build")
+                                        C.byref(lay), ptr(codes), ptr(status), stream()), "meld_pt_build")
             st = int(status.item())
             if st != 5:
                 break
@@ -1736,7 +1706,7 @@ class HipOps:
     def cheby_step(self, G, p, x_full, x_row_off, z, y, r, alpha, beta, gamma, coef, dots=None):
         check(
             self.lib.meld_cheby_step(self._operator(G), p, ptr(x_full), x_row_off, ptr(z), ptr(y), ptr(r), float(alpha), float(beta),
-                                     float(gamma), float(coef), ptr(dots), _stream()),
+                                     float(gamma), float(coef), ptr(dots), stream()),
             "meld_cheby_step",
         )
 
@@ -1745,7 +1715,7 @@ class HipOps:
         matrix streamed once for all columns)."""
         check(
             self.lib.meld_cheby_step_wide(self._operator(G, decide=False), int(p), ptr(x_full), int(x_row_off), ptr(z), ptr(y), float(alpha),
-                                          float(beta), float(gamma), _stream()),
+                                          float(beta), float(gamma), stream()),
             "meld_cheby_step_wide",
         )
 
@@ -1758,18 +1728,18 @@ class HipOps:
     def block_gram(self, A, B, n_rows, m, part, n_blocks, C):
         """``C[m, m] = A^T B`` (``meld_block_gram_f64``); ``part``: ``n_blocks * m * m`` doubles."""
         check(self.lib.meld_block_gram_f64(ptr(A), int(A.stride(0)), ptr(B), int(B.stride(0)), int(n_rows), int(m), ptr(part), int(n_blocks),
-                                           ptr(C), _stream()), "meld_block_gram_f64")
+                                           ptr(C), stream()), "meld_block_gram_f64")
 
     def block_rotate(self, A, S, n_rows, m, out):
         """``out = A S`` for ``S [m, m]`` on the device (``meld_block_rotate_f64``); ``out`` may be ``A``."""
-        check(self.lib.meld_block_rotate_f64(ptr(A), int(A.stride(0)), ptr(S), int(n_rows), int(m), ptr(out), int(out.stride(0)), _stream()),
+        check(self.lib.meld_block_rotate_f64(ptr(A), int(A.stride(0)), ptr(S), int(n_rows), int(m), ptr(out), int(out.stride(0)), stream()),
               "meld_block_rotate_f64")
 
     def block_residuals(self, LV, V, theta, n_rows, m, part, n_blocks, out):
         """``out[j] = sum_i (LV[i, j] - theta[j] V[i, j])^2`` (``meld_block_residuals_f64``); ``part``: ``n_blocks * m`` doubles."""
         assert LV.stride(0) == V.stride(0)
         check(self.lib.meld_block_residuals_f64(ptr(LV), ptr(V), int(V.stride(0)), ptr(theta), int(n_rows), int(m), ptr(part), int(n_blocks),
-                                                ptr(out), _stream()), "meld_block_residuals_f64")
+                                                ptr(out), stream()), "meld_block_residuals_f64")
 
     @staticmethod
     def _slice_begin(G, comm):
@@ -1788,7 +1758,7 @@ class HipOps:
         last = C.c_int(1)
         check(
             self.lib.meld_cheby_run(handle, self._operator(G), G.rows_pad, row_begin, p, ptr(t_prev2), ptr(t_prev1), ptr(r),
-                                    c.ctypes.data_as(C.c_void_p), int(c.shape[0]), float(alpha2), float(beta2), C.byref(last), _stream()),
+                                    c.ctypes.data_as(C.c_void_p), int(c.shape[0]), float(alpha2), float(beta2), C.byref(last), stream()),
             "meld_cheby_run",
         )
         return int(last.value)
@@ -1823,7 +1793,7 @@ class HipOps:
         check(
             self.lib.meld_lanczos_steps_sharded(handle, self._operator(G), G.rows_pad, self._slice_begin(G, comm), ptr(V[0]), ptr(V[1]),
                                                 ptr(V[2]), ptr(state), ptr(acc), ptr(alphas), ptr(betas), int(it_begin), int(n_iter),
-                                                _stream()),
+                                                stream()),
             "meld_lanczos_steps_sharded",
         )
         return True
@@ -1834,37 +1804,37 @@ class HipOps:
         that finds it nonzero does nothing (tiled layout only; the CSR kernels of small graphs run their batch out)."""
         check(
             self.lib.meld_lanczos_steps(self._operator(G), ptr(V[0]), ptr(V[1]), ptr(V[2]), ptr(state), ptr(alphas), ptr(betas),
-                                        int(it_begin), int(n_iter), ptr(scratch), ptr(stop), _stream()),
+                                        int(it_begin), int(n_iter), ptr(scratch), ptr(stop), stream()),
             "meld_lanczos_steps",
         )
 
     # the same iteration as four stream-ordered phases (row-sharded driver; see filter._lanczos_lmax_phases)
     def lanczos_spmv(self, G, x_full, z_local, y_local, state, dots):
         check(self.lib.meld_lanczos_spmv(self._operator(G), ptr(x_full), G.row_begin, ptr(z_local), ptr(y_local), ptr(state), ptr(dots),
-                                         _stream()), "meld_lanczos_spmv")
+                                         stream()), "meld_lanczos_spmv")
 
     def lanczos_alpha(self, state, dots, nrm2, alphas, it):
-        check(self.lib.meld_lanczos_alpha(ptr(state), ptr(dots), ptr(nrm2), ptr(alphas), int(it), _stream()), "meld_lanczos_alpha")
+        check(self.lib.meld_lanczos_alpha(ptr(state), ptr(dots), ptr(nrm2), ptr(alphas), int(it), stream()), "meld_lanczos_alpha")
 
     def lanczos_axpy(self, x_local, y_local, state, nrm2):
-        check(self.lib.meld_lanczos_axpy(ptr(x_local), ptr(y_local), int(x_local.shape[0]), ptr(state), ptr(nrm2), _stream()), "meld_lanczos_axpy")
+        check(self.lib.meld_lanczos_axpy(ptr(x_local), ptr(y_local), int(x_local.shape[0]), ptr(state), ptr(nrm2), stream()), "meld_lanczos_axpy")
 
     def lanczos_beta(self, state, nrm2, dots, betas, it):
-        check(self.lib.meld_lanczos_beta(ptr(state), ptr(nrm2), ptr(dots), ptr(betas), int(it), _stream()), "meld_lanczos_beta")
+        check(self.lib.meld_lanczos_beta(ptr(state), ptr(nrm2), ptr(dots), ptr(betas), int(it), stream()), "meld_lanczos_beta")
 
     # one-reduction form of the sharded iteration (filter._lanczos_lmax_folded)
     def lanczos_fold(self, state, acc, alphas, betas, it):
-        check(self.lib.meld_lanczos_fold(ptr(state), ptr(acc), ptr(alphas), ptr(betas), int(it), _stream()), "meld_lanczos_fold")
+        check(self.lib.meld_lanczos_fold(ptr(state), ptr(acc), ptr(alphas), ptr(betas), int(it), stream()), "meld_lanczos_fold")
 
     def lanczos_axpy3(self, y_local, u_local, u_prev_local, state, nrm2):
         check(self.lib.meld_lanczos_axpy3(ptr(y_local), ptr(u_local), ptr(u_prev_local), int(y_local.shape[0]), ptr(state), ptr(nrm2),
-                                          _stream()), "meld_lanczos_axpy3")
+                                          stream()), "meld_lanczos_axpy3")
 
     def scale(self, x, a, r):
-        check(self.lib.meld_scale_f64(ptr(x), float(a), ptr(r), x.numel(), _stream()), "meld_scale_f64")
+        check(self.lib.meld_scale_f64(ptr(x), float(a), ptr(r), x.numel(), stream()), "meld_scale_f64")
 
     def axpby(self, a, x, b, y, nrm2=None):
-        check(self.lib.meld_axpby_f64(float(a), ptr(x), float(b), ptr(y), y.numel(), ptr(nrm2), _stream()), "meld_axpby_f64")
+        check(self.lib.meld_axpby_f64(float(a), ptr(x), float(b), ptr(y), y.numel(), ptr(nrm2), stream()), "meld_axpby_f64")
 
 
 def metric_front_end(X, distance, decay):
@@ -1912,7 +1882,7 @@ def _exact_bandwidth(X, rows, knn, n_refs=None):
         # these by construction.  (A library norm, two ulps down, was flagged again at d = 52: "could not settle".)
         dist = torch.empty(cand.shape, dtype=torch.float64, device=X.device)
         r64 = r.to(torch.int64).contiguous()
-        check(get_lib().meld_knn_pair_distances(ptr(X), int(X.shape[1]), ptr(r64), ptr(cand), int(r64.shape[0]), kk, ptr(dist), _stream()),
+        check(get_lib().meld_knn_pair_distances(ptr(X), int(X.shape[1]), ptr(r64), ptr(cand), int(r64.shape[0]), kk, ptr(dist), stream()),
               "meld_knn_pair_distances")
         out[lo : lo + 256] = torch.sort(dist, dim=1).values[:, min(knn, kk - 1)]
     return out.clamp_(min=float(np.finfo(np.float64).eps))

@@ -31,18 +31,13 @@ SEED_ROUNDS = 5
 CHECK_EVERY = 8  # Lloyd steps between two looks of the host at the centre shift
 
 
-def _stream():
-    import torch
-
-    return torch.cuda.current_stream().cuda_stream
-
-
 def assign(Y, C, want_d2=True):
     """``(labels int32 [n], best_d2 fp64 [n] or None)``: the centre of ``C [k, d]`` nearest to every row of ``Y [n, d]`` (fp64 device
     tensors, unit stride inside a row, ``d <= MAX_D``), ties to the lowest index.  More than ``MAX_K`` centres go through the kernel
     in chunks, the label offset added and the minima combined (a later chunk wins only with a strictly smaller distance)."""
     import torch
 
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
 
     lib = get_lib()
@@ -61,7 +56,7 @@ def assign(Y, C, want_d2=True):
     lab = torch.empty(n, dtype=torch.int32, device=Y.device)
     d2 = torch.empty(n, dtype=torch.float64, device=Y.device) if (want_d2 or chunked) else None
     norms = torch.empty(min(k, MAX_K), dtype=torch.float64, device=Y.device)
-    st = _stream()
+    st = stream()
     for lo in range(0, k, MAX_K):
         Cc = C[lo : lo + MAX_K]
         first = lo == 0
@@ -81,6 +76,7 @@ def segment_sums(Y, labels, k):
     run -- the rows of a cluster are added in the order the stable sort of the labels puts them in, through fixed slots."""
     import torch
 
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
 
     n, d = int(Y.shape[0]), int(Y.shape[1])
@@ -90,7 +86,7 @@ def segment_sums(Y, labels, k):
     seg[1:] = torch.cumsum(counts, 0)
     sums = torch.zeros(k, d, dtype=torch.float64, device=Y.device)
     ldy = int(Y.stride(0)) if n > 1 else d
-    check(get_lib().meld_kmeans_wide_sums(ptr(Y), ldy, n, d, ptr(order), ptr(seg), int(k), ptr(sums), _stream()), "meld_kmeans_wide_sums")
+    check(get_lib().meld_kmeans_wide_sums(ptr(Y), ldy, n, d, ptr(order), ptr(seg), int(k), ptr(sums), stream()), "meld_kmeans_wide_sums")
     return sums, counts
 
 

@@ -89,12 +89,6 @@ def check_clusters(clusters, N):
 
 
 # -- device side ---------------------------------------------------------------------------------------------------------------
-def _stream():
-    import torch
-
-    return torch.cuda.current_stream().cuda_stream
-
-
 def merge_by_label(rowptr, col, val, n_cols, label, n_landmark, kd=None, colmap=None):
     """``(rowptr, col, val, rowsum)`` of the CSR ``[n_rows, n_landmark]`` whose row ``i`` is row ``i`` of the input with its entries
     merged by ``label`` of their column -- every present label once, ascending; values added in storage order, the diagonal
@@ -102,6 +96,7 @@ def merge_by_label(rowptr, col, val, n_cols, label, n_landmark, kd=None, colmap=
     ``colmap``: int64 device ``[n_cols]`` or None, ``label[colmap[c]]`` is the label of column ``c``."""
     import torch
 
+    from ._device_ops import scan_i32, stream
     from ._lib import check, get_lib, ptr
 
     lib, dev = get_lib(), rowptr.device
@@ -110,15 +105,11 @@ def merge_by_label(rowptr, col, val, n_cols, label, n_landmark, kd=None, colmap=
     marked = torch.empty(max(nnz + (n_rows if kd is not None else 0), 1), dtype=torch.int32, device=dev)
     if nnz == 0:  # (any address serves, none is read)
         col, val = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
-    st = _stream()
+    st = stream()
     check(lib.meld_landmark_merge_count(ptr(rowptr), ptr(col), n_rows, int(n_cols), ptr(label), int(n_landmark), ptr(colmap),
                                         0 if kd is None else 1, ptr(marked), ptr(counts), st), "meld_landmark_merge_count")
-    out_rowptr = torch.zeros(n_rows + 1, dtype=torch.int64, device=dev)
-    if n_rows:
-        tb = int(lib.meld_scan_temp_bytes(n_rows))
-        tmp = torch.empty(max(tb, 1), dtype=torch.uint8, device=dev)
-        check(lib.meld_exclusive_scan_i32_i64(ptr(counts), ptr(out_rowptr), n_rows, ptr(tmp), tb, st), "meld_exclusive_scan_i32_i64")
-    n_out = int(out_rowptr[-1]) if n_rows else 0  # (the one word the host reads)
+    out_rowptr = scan_i32(counts[:n_rows])
+    n_out = int(out_rowptr[-1])  # (the one word the host reads)
     out_col = torch.empty(max(n_out, 1), dtype=torch.int32, device=dev)
     out_val = torch.empty(max(n_out, 1), dtype=torch.float64, device=dev)
     rowsum = torch.empty(n_rows, dtype=torch.float64, device=dev)
@@ -131,6 +122,7 @@ def _gram(A, N, L):
     """``(landmark_op [L, L], s [L])`` from the merged CSR ``A = (rowptr, col, val, rowsum)`` of ``N`` cells."""
     import torch
 
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
     from .sparse import DeviceCSR
 
@@ -144,7 +136,7 @@ def _gram(A, N, L):
     has = int(col.shape[0]) > 0
     check(get_lib().meld_landmark_gram(ptr(rowptr), ptr(col if has else one_i), ptr(val if has else one_d), N, ptr(T.rowptr),
                                        ptr(T.col if has else one_i), ptr(T.val if has else one_d), L, ptr(rowsum), ptr(op), ptr(s),
-                                       _stream()), "meld_landmark_gram")
+                                       stream()), "meld_landmark_gram")
     return op, s
 
 

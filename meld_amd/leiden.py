@@ -26,9 +26,9 @@ from __future__ import annotations
 
 import torch
 
+from ._device_ops import stream
 from ._lib import check, get_lib, ptr
-from .louvain import (DEFAULT_TOL, LouvainRecord, _caller_order_csr, _check_run_arguments, _contract, _degrees, _for_n_clusters, _renumber,
-                      _run_level, _stream, _totals, q_value)
+from .louvain import DEFAULT_TOL, LouvainRecord, _community_run, _first_level, _next_level, _renumber, _run_level, _totals, q_value
 
 __all__ = ["LeidenRecord", "leiden_device"]
 
@@ -38,10 +38,6 @@ class LeidenRecord(LouvainRecord):
     ``dict(vertices, communities, subcommunities, rounds, refine_rounds, Q)`` (``communities`` and ``Q`` of the move partition,
     ``subcommunities`` of its refinement, which the next level's vertices are) and ``level_labels(l)`` the cells' refined
     sub-communities after level ``l`` (for the last level the labels returned): each level refines the next."""
-
-    def __repr__(self):
-        return "LeidenRecord(n_communities={}, modularity={:.6f}, resolution={:g}, levels={})".format(
-            self.n_communities, self.modularity, self.resolution, len(self.levels))
 
 
 def _refine(lib, st, rowptr, col, val, k, P, two_m, gamma, max_rounds):
@@ -90,17 +86,13 @@ def _singleton_q(lib, st, rowptr, col, val, n, two_m, gamma):
 
 
 def _run(G, gamma, tol, max_rounds, max_levels):
-    lib, st = get_lib(), _stream()
+    lib, st = get_lib(), stream()
     N, dev = G.N, G.rowptr.device
     cell = torch.arange(N, dtype=torch.int32, device=dev)
     levels, level_labels, q, start = [], [], 0.0, None
-    two_m = 0.0
-    if G.nnz:
-        rowptr, col, val = _caller_order_csr(G, lib, st)
-        n = N
-        k = _degrees(lib, st, rowptr, val, n)
-        two_m = float(k.sum().item())
-    while two_m > 0.0 and len(levels) < max_levels:
+    rowptr, col, val, k, two_m = _first_level(G, lib, st)
+    n = N
+    while two_m > 0.0 and len(levels) < max_levels:  # (two_m == 0: no levels)
         c, q, rounds = _run_level(lib, st, rowptr, col, val, k, two_m, gamma, tol, max_rounds, start)
         P, L, _ = _renumber(lib, st, c, k)
         if L == n:  # every community is one vertex: the partition is the one the level before moved to
@@ -123,9 +115,8 @@ def _run(G, gamma, tol, max_rounds, max_levels):
         cell = S_lab[cell.to(torch.int64)]
         level_labels.append(cell)
         start = _next_start(P, S_lab, S)
-        rowptr, col, val = _contract(lib, st, rowptr, col, val, n, S_lab, S)
+        rowptr, col, val, k = _next_level(lib, st, rowptr, col, val, n, S_lab, S)
         n = S
-        k = _degrees(lib, st, rowptr, val, n)
     sizes = torch.bincount(cell.to(torch.int64))  # (labels are numbered by smallest cell: every number below the largest occurs)
     return LeidenRecord(cell, sizes.cpu().numpy(), q, gamma, levels, level_labels)
 
@@ -133,14 +124,4 @@ def _run(G, gamma, tol, max_rounds, max_levels):
 def leiden_device(G, resolution=1.0, n_clusters=None, tol=DEFAULT_TOL, max_rounds=None, max_levels=None, recompute=False):
     """The Leiden record of ``G`` (see ``DeviceGraph.leiden``); nothing but the numbers a round reads back and the counts of a
     level goes through the host.  Kept on the graph per set of arguments."""
-    gamma, n_clusters, tol, max_rounds, max_levels = _check_run_arguments(G, "Leiden communities are", resolution, n_clusters, tol,
-                                                                          max_rounds, max_levels)
-    kept = G.__dict__.setdefault("_leiden", {})
-
-    def run(g):
-        key = (g, tol, max_rounds, max_levels)
-        if recompute or key not in kept:
-            kept[key] = _run(G, g, tol, max_rounds, max_levels)
-        return kept[key]
-
-    return _for_n_clusters(run, gamma, n_clusters)
+    return _community_run(G, "_leiden", "Leiden communities are", _run, resolution, n_clusters, tol, max_rounds, max_levels, recompute)

@@ -26,6 +26,7 @@ import math
 import numpy as np
 import torch
 
+from ._device_ops import coo_merge, csr_from_keys, scan_i32, sort_pairs, stream
 from ._graph_steps import require_unsharded
 from ._lib import check, get_lib, ptr
 
@@ -37,10 +38,6 @@ DEFAULT_MAX_LEVELS = 64
 RETRY_HALVINGS = 3  # tries with half, a quarter, an eighth of a round's movers before a level gives up
 # the resolutions the bisection for ``n_clusters`` starts from and the width at which it gives up: find_n_clusters of the reference
 R_START, R_STOP, R_TOL = 0.01, 10.0, 0.001
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 def q_value(s_in, s_tot2, two_m, gamma):
@@ -79,27 +76,15 @@ class LouvainRecord:
         return self._level_labels[level].cpu().numpy()
 
     def __repr__(self):
-        return "LouvainRecord(n_communities={}, modularity={:.6f}, resolution={:g}, levels={})".format(
-            self.n_communities, self.modularity, self.resolution, len(self.levels))
-
-
-def _sort_pairs(lib, st, keys, vals, n_ids):
-    """(keys, vals) sorted by key; keys are ``id << 32 | id`` with ids below ``n_ids``."""
-    n = int(keys.shape[0])
-    keys2, vals2 = torch.empty_like(keys), torch.empty_like(vals)
-    if n:
-        tb = lib.meld_sort_temp_bytes(n)
-        tmp = torch.empty(tb, dtype=torch.uint8, device=keys.device)
-        end_bit = 32 + max(1, int(n_ids - 1).bit_length())
-        check(lib.meld_sort_pairs_u64_f64(ptr(keys), ptr(keys2), ptr(vals), ptr(vals2), n, end_bit, ptr(tmp), tb, st), "meld_sort_pairs_u64_f64")
-    return keys2, vals2
+        return "{}(n_communities={}, modularity={:.6f}, resolution={:g}, levels={})".format(
+            type(self).__name__, self.n_communities, self.modularity, self.resolution, len(self.levels))
 
 
 def _totals(lib, st, label, k, ar):
     """``(tot, size, minm)`` of the labelling ``label`` of ``n`` vertices with degrees ``k``: the vertices grouped by label (one
-    sort), then ``meld_louvain_totals``."""
+    sort), then ``meld_louvain_totals``.  ``st`` is the CURRENT stream's handle (the sort goes to the current stream), here and below."""
     n, dev = int(label.shape[0]), label.device
-    keys, vals = _sort_pairs(lib, st, (label.to(torch.int64) << 32) | ar, k, n)
+    keys, vals = sort_pairs((label.to(torch.int64) << 32) | ar, k, n)
     tot = torch.empty(n, dtype=torch.float64, device=dev)
     size = torch.empty(n, dtype=torch.int32, device=dev)
     minm = torch.empty(n, dtype=torch.int32, device=dev)
@@ -114,18 +99,11 @@ def _contract(lib, st, rowptr, col, val, n, label, n_new, merge=True):
     nnz = int(col.shape[0])
     keys = torch.empty(nnz, dtype=torch.int64, device=dev)
     check(lib.meld_louvain_contract_keys(ptr(rowptr), ptr(col), n, ptr(label), ptr(keys), st), "meld_louvain_contract_keys")
-    keys, vals = _sort_pairs(lib, st, keys, val, n_new)
+    keys, vals = sort_pairs(keys, val, n_new)
     if merge:
-        tb = lib.meld_merge_temp_bytes(nnz)
-        tmp = torch.empty(tb, dtype=torch.uint8, device=dev)
-        n_unique = torch.zeros(1, dtype=torch.int64, device=dev)
-        ukeys, uvals = torch.empty_like(keys), torch.empty_like(vals)
-        check(lib.meld_coo_merge(ptr(keys), ptr(vals), nnz, ptr(ukeys), ptr(uvals), ptr(n_unique), ptr(tmp), tb, st), "meld_coo_merge")
-        nnz = int(n_unique.item())
-        keys, vals = ukeys, uvals[:nnz].clone()
-    out_rowptr = torch.empty(n_new + 1, dtype=torch.int64, device=dev)
-    out_col = torch.empty(nnz, dtype=torch.int32, device=dev)
-    check(lib.meld_csr_from_keys(ptr(keys), nnz, 0, n_new, ptr(out_rowptr), ptr(out_col), st), "meld_csr_from_keys")
+        keys, vals, nnz = coo_merge(keys, vals)
+        vals = vals[:nnz].clone()
+    out_rowptr, out_col = csr_from_keys(keys, nnz, 0, n_new)
     return out_rowptr, out_col, vals
 
 
@@ -175,14 +153,12 @@ def _run_level(lib, st, rowptr, col, val, k, two_m, gamma, tol, max_rounds, star
 
 def _renumber(lib, st, c, k):
     """Communities numbered by their smallest member: ``(labels int32, L, sizes int64 [L])``."""
-    from .graph import _scan_i32
-
     n, dev = int(c.shape[0]), c.device
     ar = torch.arange(n, dtype=torch.int64, device=dev)
     _, size, minm = _totals(lib, st, c, k, ar)
     flags = torch.empty(n, dtype=torch.int32, device=dev)
     check(lib.meld_louvain_heads(ptr(c), ptr(minm), n, ptr(flags), st), "meld_louvain_heads")
-    rank = _scan_i32(lib, flags, st)
+    rank = scan_i32(flags)
     L = int(rank[n].item())
     out = torch.empty(n, dtype=torch.int32, device=dev)
     sizes = torch.empty(L, dtype=torch.int64, device=dev)
@@ -212,19 +188,31 @@ def _caller_order_csr(G, lib, st):
     return _contract(lib, st, G.rowptr, G.col, G.val, G.N, G.perm.to(torch.int32), G.N, merge=False)
 
 
+def _first_level(G, lib, st):
+    """The start of a run: ``(rowptr, col, val, k, two_m)`` of ``G`` in the caller's cell order.  Where ``two_m`` is 0 the run has no
+    levels; a graph without entries yields that and no arrays."""
+    if not G.nnz:
+        return None, None, None, None, 0.0
+    rowptr, col, val = _caller_order_csr(G, lib, st)
+    k = _degrees(lib, st, rowptr, val, G.N)
+    return rowptr, col, val, k, float(k.sum().item())
+
+
+def _next_level(lib, st, rowptr, col, val, n, label, n_new):
+    """The step to the next level: ``(rowptr, col, val, k)`` of the graph contracted by ``label`` (values in ``[0, n_new)``)."""
+    rowptr, col, val = _contract(lib, st, rowptr, col, val, n, label, n_new)
+    return rowptr, col, val, _degrees(lib, st, rowptr, val, n_new)
+
+
 def _run(G, gamma, tol, max_rounds, max_levels):
-    lib, st = get_lib(), _stream()
+    lib, st = get_lib(), stream()
     N, dev = G.N, G.rowptr.device
     cell = torch.arange(N, dtype=torch.int32, device=dev)
     sizes = torch.ones(N, dtype=torch.int64, device=dev)
     levels, level_labels, q = [], [], 0.0
-    two_m = 0.0
-    if G.nnz:
-        rowptr, col, val = _caller_order_csr(G, lib, st)
-        n = N
-        k = _degrees(lib, st, rowptr, val, n)
-        two_m = float(k.sum().item())
-    while two_m > 0.0 and len(levels) < max_levels:
+    rowptr, col, val, k, two_m = _first_level(G, lib, st)
+    n = N
+    while two_m > 0.0 and len(levels) < max_levels:  # (two_m == 0: no levels)
         c, q, rounds = _run_level(lib, st, rowptr, col, val, k, two_m, gamma, tol, max_rounds)
         c, L, _ = _renumber(lib, st, c, k)
         if L == n and levels:
@@ -236,23 +224,9 @@ def _run(G, gamma, tol, max_rounds, max_levels):
             break
         # (cells per community: the sizes of the level's vertices, added by community -- integers)
         sizes = torch.zeros(L, dtype=torch.int64, device=dev).index_add_(0, c.to(torch.int64), sizes)
-        rowptr, col, val = _contract(lib, st, rowptr, col, val, n, c, L)
+        rowptr, col, val, k = _next_level(lib, st, rowptr, col, val, n, c, L)
         n = L
-        k = _degrees(lib, st, rowptr, val, n)
     return LouvainRecord(cell, sizes.cpu().numpy(), q, gamma, levels, level_labels)
-
-
-def _check_run_arguments(G, what, resolution, n_clusters, tol, max_rounds, max_levels):
-    """The arguments of a community run, checked before anything touches the device: ``(gamma, n_clusters, tol, max_rounds,
-    max_levels)`` with the defaults filled in."""
-    gamma = _check_resolution(resolution)
-    n_clusters = _positive_int("n_clusters", n_clusters, None)
-    max_rounds = _positive_int("max_rounds", max_rounds, DEFAULT_MAX_ROUNDS)
-    max_levels = _positive_int("max_levels", max_levels, DEFAULT_MAX_LEVELS)
-    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol >= 0:
-        raise ValueError("tol must be a number >= 0, got {!r}".format(tol))
-    require_unsharded(G, what)
-    return gamma, n_clusters, float(tol), max_rounds, max_levels
 
 
 def _for_n_clusters(run, gamma, n_clusters):
@@ -286,20 +260,32 @@ def _for_n_clusters(run, gamma, n_clusters):
                      "(resolution {:g})".format(R_START, R_STOP, n_clusters, n_lo, lo, n_hi, hi))
 
 
-def louvain_device(G, resolution=1.0, n_clusters=None, tol=DEFAULT_TOL, max_rounds=None, max_levels=None, recompute=False):
-    """The Louvain record of ``G`` (see ``DeviceGraph.louvain``); nothing but three numbers per round and the counts of a level
-    goes through the host.  Kept on the graph per set of arguments."""
-    gamma, n_clusters, tol, max_rounds, max_levels = _check_run_arguments(G, "Louvain communities are", resolution, n_clusters, tol,
-                                                                          max_rounds, max_levels)
-    kept = G.__dict__.setdefault("_louvain", {})
+def _community_run(G, slot, what, run_graph, resolution, n_clusters, tol, max_rounds, max_levels, recompute):
+    """What ``louvain_device`` and ``leiden_device`` share: the arguments checked before anything touches the device (``what`` words the
+    refusal of a row shard), the records of ``run_graph(G, gamma, tol, max_rounds, max_levels)`` kept in ``G.<slot>``, the bisection."""
+    gamma = _check_resolution(resolution)
+    n_clusters = _positive_int("n_clusters", n_clusters, None)
+    max_rounds = _positive_int("max_rounds", max_rounds, DEFAULT_MAX_ROUNDS)
+    max_levels = _positive_int("max_levels", max_levels, DEFAULT_MAX_LEVELS)
+    if isinstance(tol, bool) or not isinstance(tol, (int, float, np.integer, np.floating)) or not tol >= 0:
+        raise ValueError("tol must be a number >= 0, got {!r}".format(tol))
+    require_unsharded(G, what)
+    tol = float(tol)
+    kept = G.__dict__.setdefault(slot, {})
 
     def run(g):
         key = (g, tol, max_rounds, max_levels)
         if recompute or key not in kept:
-            kept[key] = _run(G, g, tol, max_rounds, max_levels)
+            kept[key] = run_graph(G, g, tol, max_rounds, max_levels)
         return kept[key]
 
     return _for_n_clusters(run, gamma, n_clusters)
+
+
+def louvain_device(G, resolution=1.0, n_clusters=None, tol=DEFAULT_TOL, max_rounds=None, max_levels=None, recompute=False):
+    """The Louvain record of ``G`` (see ``DeviceGraph.louvain``); nothing but three numbers per round and the counts of a level
+    goes through the host.  Kept on the graph per set of arguments."""
+    return _community_run(G, "_louvain", "Louvain communities are", _run, resolution, n_clusters, tol, max_rounds, max_levels, recompute)
 
 
 def louvain(G, **kwargs):
@@ -329,7 +315,7 @@ def modularity(G, labels, resolution=1.0):
     labels = _check_labels(labels, G.N)
     if G.nnz == 0:
         return 0.0
-    lib, st, dev, N = get_lib(), _stream(), G.rowptr.device, G.N
+    lib, st, dev, N = get_lib(), stream(), G.rowptr.device, G.N
     labels = labels.to(dev) if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(labels)).to(dev)
     c = torch.unique(labels, return_inverse=True)[1].to(torch.int32)  # (values in [0, L): they become addresses)
     if G.perm is not None:

@@ -22,6 +22,7 @@ import torch
 from . import filter as _filter
 from . import sparse as _sparse
 from . import utils
+from ._device_ops import stream
 from .dense import build_dense_graph, build_dense_knn_graph, build_dense_mnn_graph, build_precomputed_graph
 from .estimator import GraphEstimator, attribute, check_in, check_int, check_positive
 from .extend import attach_extension_state
@@ -276,7 +277,7 @@ class MELD(GraphEstimator):
         n, w = int(words.shape[0]), int(words.shape[1])
         if n == 0 or w > lib.meld_factorize_max_words():
             return None
-        st = torch.cuda.current_stream().cuda_stream
+        st = stream()
         t = torch.from_numpy(words).to(device)
         tb = lib.meld_factorize_temp_bytes(n)
         temp = torch.empty(tb, dtype=torch.uint8, device=device)
@@ -313,7 +314,7 @@ class MELD(GraphEstimator):
         rank[order] = np.arange(n_groups, dtype=np.int32)
         codes = torch.empty(n, dtype=torch.int64, device=device)
         lib = get_lib()
-        check(lib.meld_factorize_codes(ptr(h["temp"]), n, ptr(torch.from_numpy(rank).to(device)), ptr(codes), cur.cuda_stream), "meld_factorize_codes")
+        check(lib.meld_factorize_codes(ptr(h["temp"]), n, ptr(torch.from_numpy(rank).to(device)), ptr(codes), stream()), "meld_factorize_codes")
         counts = head[2 + G : 2 + G + n_groups][order].copy()
         return codes, uniques[order], counts
 

@@ -17,10 +17,11 @@ from types import SimpleNamespace
 
 import torch
 
+from ._device_ops import scan_i32, stream
 from ._lib import check, ptr
 from ._options import opt
 from .dense import DENSE_MAX_N
-from .graph import DeviceGraph, HipOps, _EventSpan, _scan_i32, _stream, _Timer, default_ksel, resolve_graph_params, symm_code
+from .graph import DeviceGraph, HipOps, _EventSpan, _Timer, default_ksel, resolve_graph_params, symm_code
 
 __all__ = ["build_metric_knn_graph", "cross_kernel_rows", "metric_route", "METRICS", "MAX_KNN"]
 
@@ -65,7 +66,7 @@ def build_metric_knn_graph(X, knn, decay, thresh, anisotropy, metric, kernel_sym
     knn, thresh, ksel = resolve_graph_params(N, knn, thresh, ksel)
     symm = symm_code(kernel_symm, theta)
     ops = ops if ops is not None else HipOps(X.device)
-    lib, st, dev = ops.lib, _stream(), X.device
+    lib, st, dev = ops.lib, stream(), X.device
     code = METRICS[metric]
     prune = opt("MELD_METRIC_PRUNE", "1") != "0"  # (development switch: the unpruned search for A-B comparisons)
     tm = _Timer(profile)
@@ -108,7 +109,7 @@ def build_metric_knn_graph(X, knn, decay, thresh, anisotropy, metric, kernel_sym
     check(lib.meld_metric_refine(ptr(cand_idx), ptr(cand_d), ptr(cand_cnt), N, ksel, knn, decay, thresh, ptr(r.bw), ptr(r.cand_val),
                                  ptr(r.keep_cnt), ptr(r.flag_rows), ptr(n_flag), st), "meld_metric_refine")
     del cand_d
-    r.keep_off = _scan_i32(lib, r.keep_cnt, st)
+    r.keep_off = scan_i32(r.keep_cnt)
     n_flag_h, m_main, done_h = torch.stack([n_flag[0].to(torch.int64), r.keep_off[N], tiles_done[0]]).tolist()  # (one read-back)
     r.n_flag, r.m_main = int(n_flag_h), int(m_main)
     tm.stop("refine")
@@ -157,7 +158,7 @@ def _radius_sweep(lib, st, X, N, d, code, r, decay, thresh):
     fb_cnt = torch.zeros(n_flag, dtype=torch.int32, device=dev)
     check(lib.meld_metric_radius(ptr(X), N, d, code, ptr(flag_rows), n_flag, ptr(r.bw), decay, thresh, 0, ptr(fb_cnt), None, None, None, None, st),
           "meld_metric_radius(count)")
-    fb_off = _scan_i32(lib, fb_cnt, st)
+    fb_off = scan_i32(fb_cnt)
     fb_total, most = (int(v) for v in torch.stack([fb_off[n_flag], fb_cnt.max().to(torch.int64)]).tolist())
     if most + 1 > N / 2:
         # a kernel radius that holds most of the data (many copies of one cell, a radius wider than the data): the graph is dense,
@@ -201,7 +202,7 @@ def reference_cache(G, st):
     n_tiles = (N + T - 1) // T
     box_lo = torch.empty(n_tiles * d, dtype=torch.float64, device=dev)
     box_hi = torch.empty(n_tiles * d, dtype=torch.float64, device=dev)
-    check(lib.meld_metric_tile_boxes(ptr(Xp), N, d, ptr(box_lo), ptr(box_hi), _stream()), "meld_metric_tile_boxes")
+    check(lib.meld_metric_tile_boxes(ptr(Xp), N, d, ptr(box_lo), ptr(box_hi), stream()), "meld_metric_tile_boxes")
     st._refs = SimpleNamespace(X=Xp, perm=perm, box_lo=box_lo, box_hi=box_hi, n_tiles=n_tiles, tile=T, ops=ops)
     return st._refs
 
@@ -232,7 +233,7 @@ def cross_kernel_rows(G, st, Q, knn_c, decay, thresh, bandwidth=None, scale=1.0,
     if knn_c > ksel:
         raise NotImplementedError("knn={} beyond the {} entries the candidate lists hold".format(knn_c, ksel))
     refs = reference_cache(G, st)
-    ops, lib, stream, dev = refs.ops, refs.ops.lib, _stream(), Q.device
+    ops, lib, launch, dev = refs.ops, refs.ops.lib, stream(), Q.device
     Xp, N, d, M = refs.X, int(refs.X.shape[0]), int(refs.X.shape[1]), int(Q.shape[0])
     code = int(st.metric)
     prune = opt("MELD_METRIC_PRUNE", "1") != "0"
@@ -255,7 +256,7 @@ def cross_kernel_rows(G, st, Q, knn_c, decay, thresh, bandwidth=None, scale=1.0,
             # few tiles and share a small box
             Qt = Qc.t().contiguous()  # [d][m]: lane = query, the reads of one coordinate coalesce
             seed_key = torch.full((m,), -1, dtype=torch.int64, device=dev)
-            check(lib.meld_metric_cross_seed(ptr(Qt), m, ptr(refs.box_lo), ptr(refs.box_hi), N, d, code, ptr(seed_key), stream),
+            check(lib.meld_metric_cross_seed(ptr(Qt), m, ptr(refs.box_lo), ptr(refs.box_hi), N, d, code, ptr(seed_key), launch),
                   "meld_metric_cross_seed")
             seed, order = torch.sort(seed_key & 0xFFFFFFFF, stable=True)
             seed = seed.to(torch.int32)
@@ -277,7 +278,7 @@ def cross_kernel_rows(G, st, Q, knn_c, decay, thresh, bandwidth=None, scale=1.0,
             with _EventSpan("metric_cross_topk", M=m, N=N, d=d, slices=ns):
                 check(lib.meld_metric_cross_topk(ptr(Qt), m, ptr(Xp), N, d, code, ksel, ptr(refs.box_lo), ptr(refs.box_hi), ptr(seed), int(prune),
                                                  ns, ptr(heap_d), ptr(heap_i), ptr(part_idx), ptr(part_d), ptr(part_cnt), ptr(cand_idx),
-                                                 ptr(cand_d), ptr(cand_cnt), ptr(tiles_done), stream), "meld_metric_cross_topk")
+                                                 ptr(cand_d), ptr(cand_cnt), ptr(tiles_done), launch), "meld_metric_cross_topk")
             del heap_d, heap_i, part_idx, part_d, part_cnt, Qt
             r.bw = torch.empty(m, dtype=torch.float64, device=dev)
             cand_val = torch.empty(m * ksel, dtype=torch.float64, device=dev)
@@ -285,7 +286,7 @@ def cross_kernel_rows(G, st, Q, knn_c, decay, thresh, bandwidth=None, scale=1.0,
             r.flag_rows = torch.empty(m, dtype=torch.int32, device=dev)
             n_flag = torch.zeros(1, dtype=torch.int32, device=dev)
             check(lib.meld_metric_cross_refine(ptr(cand_idx), ptr(cand_d), ptr(cand_cnt), m, ksel, knn_c - 1, decay, thresh, float(scale),
-                                               ptr(r.bw), ptr(cand_val), ptr(keep_cnt), ptr(r.flag_rows), ptr(n_flag), stream),
+                                               ptr(r.bw), ptr(cand_val), ptr(keep_cnt), ptr(r.flag_rows), ptr(n_flag), launch),
                   "meld_metric_cross_refine")
             del cand_d
             n_flag_h, done_h = torch.stack([n_flag[0].to(torch.int64), tiles_done[0]]).tolist()  # (one read-back)
@@ -299,7 +300,7 @@ def cross_kernel_rows(G, st, Q, knn_c, decay, thresh, bandwidth=None, scale=1.0,
             stats["tile_pairs"] += ((m + refs.tile - 1) // refs.tile) * refs.n_tiles
             stats["n_slices"].append(ns)
             del cand_idx, cand_val, kept
-        s = _cross_radius_sweep(lib, stream, Qc, Xp, N, d, code, r, decay, thresh)
+        s = _cross_radius_sweep(lib, launch, Qc, Xp, N, d, code, r, decay, thresh)
         stats["n_flagged_rows"] += r.n_flag
         if s.fb_total:
             rows = torch.repeat_interleave(r.flag_rows.to(torch.int64), s.fb_cnt.to(torch.int64), output_size=s.fb_total)
@@ -326,7 +327,7 @@ def _cross_radius_sweep(lib, st, Q, X, N, d, code, r, decay, thresh):
     fb_cnt = torch.zeros(n_flag, dtype=torch.int32, device=dev)
     check(lib.meld_metric_cross_radius(ptr(Q), m, ptr(X), N, d, code, ptr(flag_rows), n_flag, ptr(r.bw), decay, thresh, 0, ptr(fb_cnt), None, None,
                                        None, None, st), "meld_metric_cross_radius(count)")
-    fb_off = _scan_i32(lib, fb_cnt, st)
+    fb_off = scan_i32(fb_cnt)
     fb_total = int(fb_off[n_flag])
     need = 12 * fb_total + 48 * (r.m_main + fb_total)
     if need > torch.cuda.get_device_properties(dev).total_memory:

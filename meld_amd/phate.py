@@ -129,18 +129,13 @@ def sign_columns(Z):
 
 
 # -- device side ---------------------------------------------------------------------------------------------------------------
-def _stream():
-    import torch
-
-    return torch.cuda.current_stream().cuda_stream
-
-
 def operator_device(G):
     """The graph's ``diff_op = D^-1 (W + diag(kd))`` as a dense fp64 device tensor ``[N, N]``, rows and columns in the device order
     (the direct route's operator)."""
     import torch
 
     from ._graph_steps import csr_operands
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
     from .diffuse import walk_vectors
 
@@ -150,7 +145,7 @@ def operator_device(G):
     P = torch.empty(N, N, dtype=torch.float64, device=G.val.device)
     rowptr, col, val = csr_operands(G, G.val)
     check(get_lib().meld_csr_rows_to_dense_f64(ptr(rowptr), ptr(col), ptr(val), 1 if val.dtype == torch.float32 else 0, 0, N, N, ptr(P), N,
-                                               _stream()), "meld_csr_rows_to_dense_f64")
+                                               stream()), "meld_csr_rows_to_dense_f64")
     P.diagonal().add_(kd)
     P /= s[:, None]
     return P
@@ -236,6 +231,7 @@ def classical_mds_device(Dm, n_components):
 def smacof_step_device(Dm, Z, Z_out, row_stress):
     """One launch of ``meld_smacof_step``: ``Z_out`` <- the Guttman transform of ``Z`` towards ``Dm`` (any row stride), ``row_stress``
     <- the stress terms of ``Z``."""
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
 
     n, dim = int(Z.shape[0]), int(Z.shape[1])
@@ -246,7 +242,7 @@ def smacof_step_device(Dm, Z, Z_out, row_stress):
             or int(row_stress.shape[0]) != n:
         raise ValueError("Z, Z_out [n, dim] and row_stress [n] must be contiguous and of matching shapes")
     ld = int(Dm.stride(0)) if n > 1 else max(n, 1)
-    check(get_lib().meld_smacof_step(ptr(Dm), ld, n, dim, ptr(Z), ptr(Z_out), ptr(row_stress), _stream()), "meld_smacof_step")
+    check(get_lib().meld_smacof_step(ptr(Dm), ld, n, dim, ptr(Z), ptr(Z_out), ptr(row_stress), stream()), "meld_smacof_step")
 
 
 def smacof_device(Dm, Z0, max_iter=3000, eps=1e-6):

@@ -161,8 +161,8 @@ def row_stats_device(A, col_mask=None, cutoff=0.0):
     ``col_mask``: a uint8 / bool device tensor [G], the statistics then cover its columns only."""
     import torch
 
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
-    from .sparse import _stream
 
     N, G = A.shape
     dev = A.device
@@ -174,7 +174,7 @@ def row_stats_device(A, col_mask=None, cutoff=0.0):
         if int(col_mask.shape[0]) != G:
             raise ValueError("row_stats: a column mask of {} entries for {} columns".format(int(col_mask.shape[0]), G))
     mat, hold = _arrays(A)
-    check(get_lib().meld_prep_row_stats(*mat, ptr(col_mask), float(cutoff), ptr(s), ptr(a), ptr(c), _stream()), "meld_prep_row_stats")
+    check(get_lib().meld_prep_row_stats(*mat, ptr(col_mask), float(cutoff), ptr(s), ptr(a), ptr(c), stream()), "meld_prep_row_stats")
     del hold
     return s, a, c
 
@@ -183,8 +183,8 @@ def col_counts_device(A, row_keep=None, cutoff=0.0):
     """int32 device tensor [G]: per column the entries above ``cutoff`` in the rows ``row_keep`` keeps (uint8 / bool [N]; None: all)."""
     import torch
 
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
-    from .sparse import _stream
 
     N, G = A.shape
     count = torch.zeros(G, dtype=torch.int32, device=A.device)
@@ -193,7 +193,7 @@ def col_counts_device(A, row_keep=None, cutoff=0.0):
         if int(row_keep.shape[0]) != N:
             raise ValueError("col_counts: a row mask of {} entries for {} rows".format(int(row_keep.shape[0]), N))
     mat, hold = _arrays(A)
-    check(get_lib().meld_prep_col_counts(*mat, ptr(row_keep), float(cutoff), ptr(count), _stream()), "meld_prep_col_counts")
+    check(get_lib().meld_prep_col_counts(*mat, ptr(row_keep), float(cutoff), ptr(count), stream()), "meld_prep_col_counts")
     del hold
     return count
 
@@ -206,11 +206,11 @@ def select(A, rows=None, cols=None, scale=None, rescale=1.0, transform=None, cof
     import torch
 
     from . import sparse as _sp
+    from ._device_ops import scan_i32, stream
     from ._lib import check, get_lib, ptr
-    from .sparse import _stream
 
     code = _transform_code(transform)
-    lib, st, dev = get_lib(), _stream(), A.device
+    lib, st, dev = get_lib(), stream(), A.device
     N, G = A.shape
     if rows is None:
         rows_d = torch.arange(N, dtype=torch.int32, device=dev)
@@ -234,10 +234,7 @@ def select(A, rows=None, cols=None, scale=None, rescale=1.0, transform=None, cof
     mat, hold = _arrays(A)
     counts = torch.empty(n_keep, dtype=torch.int32, device=dev)
     check(lib.meld_prep_select_count(mat[0], mat[1], N, G, ptr(rows_d), n_keep, ptr(col_map), ptr(counts), st), "meld_prep_select_count")
-    rowptr = torch.empty(n_keep + 1, dtype=torch.int64, device=dev)
-    tb = int(lib.meld_scan_temp_bytes(n_keep))
-    tmp = torch.empty(tb, dtype=torch.uint8, device=dev)
-    check(lib.meld_exclusive_scan_i32_i64(ptr(counts), ptr(rowptr), n_keep, ptr(tmp), tb, st), "meld_exclusive_scan_i32_i64")
+    rowptr = scan_i32(counts)
     nnz = int(rowptr[-1])
     out_col = torch.empty(nnz, dtype=torch.int32, device=dev)
     out_val = torch.empty(nnz, dtype=torch.float64, device=dev)
@@ -245,7 +242,7 @@ def select(A, rows=None, cols=None, scale=None, rescale=1.0, transform=None, cof
     if nnz:
         check(lib.meld_prep_select_fill(*mat, ptr(rows_d), n_keep, ptr(col_map), ptr(scale), float(rescale), code, float(cofactor),
                                         ptr(rowptr), ptr(out_col), ptr(out_val), ptr(out_norm), st), "meld_prep_select_fill")
-    del hold, tmp, counts
+    del hold, counts
     cells = A.cell_index if rows_h is None or A.cell_index is None else np.asarray(A.cell_index)[rows_h]
     genes = A.gene_names if cols_h is None or A.gene_names is None else np.asarray(A.gene_names)[cols_h]
     out = _sp.DeviceCSR(rowptr, out_col, out_val, (n_keep, n_cols_out))

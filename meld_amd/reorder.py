@@ -21,6 +21,7 @@ import os
 import numpy as np
 import torch
 
+from ._device_ops import stream
 from ._lib import check, get_lib, ptr
 
 __all__ = ["locality_permutation"]
@@ -71,7 +72,7 @@ def locality_permutation(X, c1=None, fanouts=None, seed=0, comm=None):
     if opt("MELD_REORDER"):  # tuning hook: "c1,f1,f2,..."
         parts = [int(v) for v in opt("MELD_REORDER").split(",")]
         c1, fanouts = parts[0], tuple(parts[1:])
-    st = torch.cuda.current_stream().cuda_stream
+    st = stream()
     dev = X.device
     if c1 is None:
         c1 = int(min(64, max(8, N // 4096)))
@@ -101,7 +102,7 @@ def locality_permutation(X, c1=None, fanouts=None, seed=0, comm=None):
         side.wait_stream(main)
         with torch.cuda.stream(side):
             if f > 2:
-                check(lib.meld_chain_order(ptr(cents), n_groups, f, d, ptr(rank), side.cuda_stream), "meld_chain_order")
+                check(lib.meld_chain_order(ptr(cents), n_groups, f, d, ptr(rank), stream()), "meld_chain_order")  # (current here: side)
             else:
                 rank.copy_(torch.arange(f, **i32).repeat(n_groups))
         if comm is None or comm.world == 1:

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import pca as _pca
+from ._device_ops import csr_from_keys, sort_pairs, stream
 from ._lib import check, get_lib, ptr
 
 __all__ = ["is_sparse_input", "to_host_csr", "DeviceCSR", "truncated_svd_project", "reduce_data"]
@@ -83,10 +84,6 @@ def to_host_csr(X):
         A = A.copy()
         A.sum_duplicates()
     return A
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
 
 
 class DeviceCSR:
@@ -196,7 +193,7 @@ class DeviceCSR:
         check(get_lib().meld_csr_spmm_f64(ptr(self.rowptr), ptr(self.col), ptr(self.val), self.val_f32, self.shape[0],
                                           ptr(p["unit_row"]), ptr(p["unit_off"]), p["n_units"], ptr(p["part_off"]),
                                           ptr(p["split_rows"]), int(p["split_rows"].shape[0]), ptr(partial), ptr(B),
-                                          int(B.stride(0)), r, ptr(Y), int(Y.stride(0)), _stream()), "meld_csr_spmm_f64")
+                                          int(B.stride(0)), r, ptr(Y), int(Y.stride(0)), stream()), "meld_csr_spmm_f64")
         return Y
 
     # ---- the transpose (CSC of X as the CSR of X^T) --------------------------------------------------------------------
@@ -211,14 +208,12 @@ class DeviceCSR:
         return self._T
 
     def _transpose(self):
-        lib, st, dev = get_lib(), _stream(), self.device
+        lib, st, dev = get_lib(), stream(), self.device
         N, G = self.shape
         nnz = self.nnz
-        rowptr = torch.empty(G + 1, dtype=torch.int64, device=dev)
-        col = torch.empty(nnz, dtype=torch.int32, device=dev)
         if nnz == 0:
-            rowptr.zero_()
-            return DeviceCSR(rowptr, col, torch.empty(0, dtype=torch.float64, device=dev), (G, N))
+            return DeviceCSR(torch.zeros(G + 1, dtype=torch.int64, device=dev), torch.empty(0, dtype=torch.int32, device=dev),
+                             torch.empty(0, dtype=torch.float64, device=dev), (G, N))
         need = self.transpose_bytes()
         free, _ = torch.cuda.mem_get_info(dev)
         if need > free + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev):
@@ -228,15 +223,9 @@ class DeviceCSR:
         vals = torch.empty(nnz, dtype=torch.float64, device=dev)
         check(lib.meld_csr_transpose_keys(ptr(self.rowptr), ptr(self.col), ptr(self.val), self.val_f32, N, ptr(keys), ptr(vals), st),
               "meld_csr_transpose_keys")
-        keys2, vals2 = torch.empty_like(keys), torch.empty_like(vals)
-        tb = lib.meld_sort_temp_bytes(nnz)
-        tmp = torch.empty(tb, dtype=torch.uint8, device=dev)
-        end_bit = 32 + max(1, int(G - 1).bit_length())
-        check(lib.meld_sort_pairs_u64_f64(ptr(keys), ptr(keys2), ptr(vals), ptr(vals2), nnz, end_bit, ptr(tmp), tb, st),
-              "meld_sort_pairs_u64_f64")
-        del keys, vals, tmp
-        check(lib.meld_csr_from_keys(ptr(keys2), nnz, 0, G, ptr(rowptr), ptr(col), st), "meld_csr_from_keys")
-        return DeviceCSR(rowptr, col, vals2, (G, N))
+        keys, vals = sort_pairs(keys, vals, G)  # (the unsorted keys and values are released here, the sort's scratch before)
+        rowptr, col = csr_from_keys(keys, nnz, 0, G)
+        return DeviceCSR(rowptr, col, vals, (G, N))
 
     # ---- densification -------------------------------------------------------------------------------------------------
     def rows_to_dense(self, lo, hi, out=None):
@@ -245,7 +234,7 @@ class DeviceCSR:
         if out is None:
             out = torch.empty(hi - lo, G, dtype=torch.float64, device=self.device)
         check(get_lib().meld_csr_rows_to_dense_f64(ptr(self.rowptr), ptr(self.col), ptr(self.val), self.val_f32, int(lo), int(hi - lo),
-                                                   G, ptr(out), int(out.stride(0)), _stream()), "meld_csr_rows_to_dense_f64")
+                                                   G, ptr(out), int(out.stride(0)), stream()), "meld_csr_rows_to_dense_f64")
         return out
 
     def to_dense(self):

@@ -115,9 +115,10 @@ def partial_basis_device(G, k, tol=1e-6, max_iter=200, seed=0):
     """The ``k`` smallest eigenpairs of ``G``'s Laplacian as device tensors ``(e [k], U [N, k], info)``, ``e`` ascending, the rows
     of ``U`` in the caller's order, signs fixed (``fix_signs``).  RuntimeError, stating the worst residual reached, when the
     ``k`` smallest Ritz pairs do not all reach ``|L v - theta v| <= tol * ub`` within ``max_iter`` filter applications."""
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
     from .filter import _ops_of
-    from .graph import _EventSpan, _stream
+    from .graph import _EventSpan
 
     k = check_k(k)
     if G.n_rows != G.N:
@@ -192,7 +193,7 @@ def partial_basis_device(G, k, tol=1e-6, max_iter=200, seed=0):
         U = Vk
     else:
         U = torch.empty_like(Vk)
-        check(get_lib().meld_scatter_rows_f64(ptr(Vk), ptr(G.perm), N, k, ptr(U), _stream()), "meld_scatter_rows_f64")
+        check(get_lib().meld_scatter_rows_f64(ptr(Vk), ptr(G.perm), N, k, ptr(U), stream()), "meld_scatter_rows_f64")
     info = dict(method="chebyshev-filtered subspace iteration", n=N, k=k, block=m, ub=ub, ub_rule=rule, tol=float(tol), seed=int(seed),
                 iterations=len(degrees), degrees=degrees, wide_steps=sum(degrees) + len(degrees) + 1, worst_residual=worst)
     return e, fix_signs(U), info

@@ -67,6 +67,7 @@ def normalize_densities(sample_densities):
     one-pass HIP kernel (``meld_normalize_rows_l1``)."""
     import torch
 
+    from ._device_ops import stream
     from ._lib import check, get_lib, ptr
 
     is_df = isinstance(sample_densities, pd.DataFrame)
@@ -81,7 +82,7 @@ def normalize_densities(sample_densities):
     x = torch.from_numpy(arr).to("cuda")
     out = torch.empty_like(x)
     check(
-        lib.meld_normalize_rows_l1(ptr(x), ptr(out), arr.shape[0], arr.shape[1], torch.cuda.current_stream().cuda_stream),
+        lib.meld_normalize_rows_l1(ptr(x), ptr(out), arr.shape[0], arr.shape[1], stream()),
         "meld_normalize_rows_l1",
     )
     res = out.cpu().numpy()

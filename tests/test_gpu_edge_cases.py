@@ -263,3 +263,30 @@ def test_a_radius_that_covers_the_data_is_refused_with_an_explanation():
     X = torch.from_numpy(rng.normal(size=(150_000, 12))).cuda()
     with pytest.raises(MemoryError, match="raise decay or thresh"):
         meld_amd.build_knn_graph(X, knn=18, decay=2, thresh=1e-6)
+
+
+@pytest.mark.parametrize("n", [0, 1, 257])
+def test_scan_primitive(n):
+    """``_device_ops.scan_i32``: the exclusive scan with the total behind it, an empty input included."""
+    from meld_amd._device_ops import scan_i32
+
+    x = np.random.default_rng(n).integers(0, 1000, size=n).astype(np.int32)
+    out = scan_i32(torch.from_numpy(x).cuda())
+    assert out.dtype == torch.int64 and tuple(out.shape) == (n + 1,)
+    assert np.array_equal(out.cpu().numpy(), np.concatenate([[0], np.cumsum(x, dtype=np.int64)]))
+
+
+@pytest.mark.parametrize("n_ids", [1, 5003])
+@pytest.mark.parametrize("n", [0, 1, 300])
+def test_sort_pairs_primitive(n, n_ids):
+    """``_device_ops.sort_pairs`` on ``id << 32 | id`` keys against a stable argsort: with one id every key is the same and the sorted
+    bits end at their floor; with 5003 ids the keys are spread."""
+    from meld_amd._device_ops import sort_pairs
+
+    rng = np.random.default_rng(n + n_ids)
+    hi, lo = rng.integers(0, n_ids, size=n), rng.integers(0, min(n_ids, 3), size=n)
+    keys = (hi.astype(np.int64) << 32) | lo
+    vals = rng.normal(size=n)
+    k2, v2 = sort_pairs(torch.from_numpy(keys).cuda(), torch.from_numpy(vals).cuda(), n_ids)
+    order = np.argsort(keys, kind="stable")
+    assert np.array_equal(k2.cpu().numpy(), keys[order]) and np.array_equal(v2.cpu().numpy(), vals[order])

@@ -99,6 +99,38 @@ def test_a_row_whose_neighbours_lie_in_other_communities_stays():
         assert np.array_equal(prop, w_prop) and np.array_equal(new, w_new) and movers == w_movers, lanes
 
 
+def _hub_outside_its_community():
+    """``(W, P, k)``: hub_300 with everyone in one community, except the hub's neighbours beyond its first three, each alone."""
+    W = _graph("hub_300")
+    hub = 4096
+    nbrs = W.indices[W.indptr[hub] : W.indptr[hub + 1]]
+    P = np.zeros(W.shape[0], dtype=np.int64)
+    P[nbrs[3:]] = 1 + np.arange(nbrs.shape[0] - 3)
+    return W, lref.renumber(P)[0], lref.degrees(W)
+
+
+def test_a_long_row_that_is_not_well_connected_leaves_after_its_first_chunk():
+    """The hub's row of 300 entries takes five chunks at 16 lanes per row and two at 64; three of its entries lie in its community,
+    which is far too little for its degree: the row meets all its entries with the first chunk, proposes nothing and scores
+    nothing, while the rest of the graph moves."""
+    W, P, k = _hub_outside_its_community()
+    n, hub, gamma = W.shape[0], 4096, 1.0
+    two_m = float(k.sum())
+    lo, hi = W.indptr[hub], W.indptr[hub + 1]
+    cols, vals = W.indices[lo:hi], W.data[lo:hi]
+    inside = (P[cols] == P[hub]) & (cols != hub)
+    in_c = float(vals[inside].sum())
+    tot_c = float(k[P == P[hub]].sum())
+    assert hi - lo > 256  # (more than one chunk at 64 lanes per row, more than four at 16)
+    assert in_c > 0 and in_c * two_m < gamma * k[hub] * (tot_c - k[hub])
+    sub = np.arange(n, dtype=np.int64)
+    w_new, w_prop, w_movers = ref.refine_round(W, P, sub, k, two_m, gamma, 0)
+    assert w_prop[hub] == -1 and w_movers > 0
+    for lanes in (16, 64):
+        new, prop, movers = _device_round(W, P, sub, gamma, 0, lanes)
+        assert np.array_equal(prop, w_prop) and np.array_equal(new, w_new) and movers == w_movers, lanes
+
+
 def _assert_record_equals(rec, want, what):
     assert rec.labels.dtype == np.int32 and np.array_equal(rec.labels, want["labels"]), what
     assert rec.levels == want["levels"], (what, rec.levels, want["levels"])

@@ -187,8 +187,8 @@ def test_leiden_kernels_do_not_spill():
     for name, r in kernels.items():
         assert r["ScratchSize [bytes/lane]:"] == 0, (name, r)
         if "leiden_propose" in name:
-            # reported: 68 VGPRs at 16 lanes per row, 70 at 64, 7 waves per SIMD both (four entries per lane with their sums, as
-            # louvain_move_kernel; up to 72 registers keep the seventh wave)
+            # reported: 68 VGPRs at 16 lanes per row, 70 at 64, 7 waves per SIMD both (four entries per lane with their sums: the
+            # row pass of label_rows.hpp in its LOCAL form; up to 72 registers keep the seventh wave)
             assert r["VGPRs:"] <= 72 and r["Occupancy [waves/SIMD]:"] >= 7, (name, r)
         else:  # reported: 8 (commit) and 10 (count) VGPRs, 8 waves per SIMD
             assert r["VGPRs:"] <= 16 and r["Occupancy [waves/SIMD]:"] == 8, (name, r)

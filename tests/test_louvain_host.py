@@ -199,7 +199,7 @@ def test_louvain_kernels_do_not_spill():
     assert len(kernels) == 8, sorted(rows)  # (the move kernel at 16 and at 64 lanes per row)
     for name, r in kernels.items():
         assert r["ScratchSize [bytes/lane]:"] == 0, (name, r)
-        if "louvain_move" in name:  # (four entries per lane with their sums: past 64 registers, one wave per SIMD fewer)
+        if "louvain_move" in name:  # (reported: 64 VGPRs at 16 and at 64 lanes per row, 8 waves per SIMD; past 64 registers, one wave fewer)
             assert r["VGPRs:"] <= 80 and r["Occupancy [waves/SIMD]:"] >= 6, (name, r)
         else:
             assert r["VGPRs:"] <= 64 and r["Occupancy [waves/SIMD]:"] == 8, (name, r)
