@@ -1,4 +1,4 @@
-"""The small device primitives the host modules share: the stream every launch goes to, the exclusive scan, the radix sort of
+"""The small device primitives the host modules share: the stream every launch goes to, the tall Gram, the exclusive scan, the radix sort of
 ``id << 32 | id`` keys, the reduce-by-key behind it and the CSR assembly from sorted keys; their scratch is sized and released
 here."""
 from __future__ import annotations
@@ -11,6 +11,20 @@ from ._lib import check, get_lib, ptr
 def stream():
     """The current torch stream as the handle the library takes; the functions below launch on it."""
     return torch.cuda.current_stream().cuda_stream
+
+
+def tall_gram(A, B, chunk=4096):
+    """A^T B for tall-skinny A [n, r], B [n, s] (n ~ 1e6, r, s ~ 64): as a batch of chunk-row products summed at the end.
+    The library GEMM runs this shape -- a 64 x 64 result with a million-long inner dimension -- on a handful of
+    workgroups (54 ms at 1M x 64); split over the inner dimension it is bandwidth-bound (~1 ms)."""
+    n = A.shape[0]
+    nb = n // chunk
+    out = torch.zeros(A.shape[1], B.shape[1], dtype=A.dtype, device=A.device)
+    if nb > 0:
+        out += torch.bmm(A[: nb * chunk].view(nb, chunk, -1).transpose(1, 2), B[: nb * chunk].view(nb, chunk, -1)).sum(0)
+    if nb * chunk < n:
+        out += A[nb * chunk :].T @ B[nb * chunk :]
+    return out
 
 
 def scan_i32(x):

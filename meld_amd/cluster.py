@@ -37,8 +37,8 @@ path's sizes.  Two methods (``method=``):
     reference-style spectrogram with heat windows (tested).  Cost: 2 chebyshev_order + 1 SpMMs of n_probes
     columns, independent of n_windows x n_bands.
 
-PCA (``meld_amd.pca``) and a seeded k-means++ / Lloyd KMeans follow (assignment + centroid update in
-``csrc/kmeans.hip``).  Same constructor, methods, checks and messages as the reference class.
+PCA (``meld_amd.pca``) and a seeded k-means++ / Lloyd KMeans follow: ``meld_amd.kmeans.kmeans_device`` with the k-means++ seeder
+and the LDS step of ``csrc/kmeans.hip`` preferred (the library step beyond 32 features / 64 clusters).  Same constructor, methods, checks and messages as the reference class.
 """
 from __future__ import annotations
 
@@ -51,7 +51,8 @@ import pandas as pd
 import torch
 
 from . import utils
-from ._device_ops import stream
+from ._device_ops import tall_gram
+from .kmeans import kmeans_device
 
 __all__ = ["VertexFrequencyCluster"]
 
@@ -59,111 +60,6 @@ __all__ = ["VertexFrequencyCluster"]
 def _l2_normalize_columns(M):
     nrm = torch.linalg.vector_norm(M, dim=0, keepdim=True)
     return M / torch.where(nrm == 0, torch.ones_like(nrm), nrm)
-
-
-def _lloyd_step(Y, C, lab, scratch):
-    """One Lloyd iteration on the device (``meld_kmeans_assign``): labels of the nearest centroid, new centroids
-    (an empty cluster keeps its centroid), inertia of the assignment -- all as device tensors, no sync."""
-    from ._lib import check, get_lib, ptr
-
-    lib = get_lib()
-    n, d = Y.shape
-    k = C.shape[0]
-    nb = scratch["nb"]
-    check(lib.meld_kmeans_assign(ptr(Y), n, d, ptr(C), k, ptr(lab), ptr(scratch["sum"]), ptr(scratch["cnt"]), ptr(scratch["in"]),
-                                 nb, stream()), "meld_kmeans_assign")
-    sums = scratch["sum"].view(nb, k, d).sum(0)  # fixed-order reduction of the per-workgroup partials
-    cnt = scratch["cnt"].view(nb, k).sum(0)
-    newC = torch.where(cnt[:, None] > 0, sums / cnt.clamp(min=1.0)[:, None], C)
-    return newC, scratch["in"].sum()
-
-
-def _tall_gram(A, B, chunk=4096):
-    """A^T B for tall-skinny A [n, r], B [n, s] (n ~ 1e6, r, s ~ 64): as a batch of chunk-row products summed at the end.
-    The library GEMM runs this shape -- a 64 x 64 result with a million-long inner dimension -- on a handful of
-    workgroups (54 ms at 1M x 64); split over the inner dimension it is bandwidth-bound (~1 ms)."""
-    n = A.shape[0]
-    nb = n // chunk
-    out = torch.zeros(A.shape[1], B.shape[1], dtype=A.dtype, device=A.device)
-    if nb > 0:
-        out += torch.bmm(A[: nb * chunk].view(nb, chunk, -1).transpose(1, 2), B[: nb * chunk].view(nb, chunk, -1)).sum(0)
-    if nb * chunk < n:
-        out += A[nb * chunk :].T @ B[nb * chunk :]
-    return out
-
-
-def _lloyd_step_library(Y, C, lab):
-    """``_lloyd_step`` for shapes beyond the HIP kernel (d > 32 or k > 64): chunked distance GEMMs, argmin (ties to the
-    lowest index), index_add for the sums -- same outputs."""
-    n, d = Y.shape
-    k = C.shape[0]
-    c2 = (C * C).sum(1)
-    sums = torch.zeros(k, d, dtype=Y.dtype, device=Y.device)
-    cnt = torch.zeros(k, dtype=Y.dtype, device=Y.device)
-    inertia = torch.zeros((), dtype=Y.dtype, device=Y.device)
-    for lo in range(0, n, 1 << 18):
-        Yc = Y[lo : lo + (1 << 18)]
-        d2 = (Yc * Yc).sum(1)[:, None] + c2[None, :] - 2.0 * (Yc @ C.T)
-        best, idx = torch.min(d2, dim=1)
-        lab[lo : lo + Yc.shape[0]] = idx.to(lab.dtype)
-        sums.index_add_(0, idx, Yc)
-        cnt.index_add_(0, idx, torch.ones_like(best))
-        inertia = inertia + best.clamp_(min=0.0).sum()
-    newC = torch.where(cnt[:, None] > 0, sums / cnt.clamp(min=1.0)[:, None], C)
-    return newC, inertia
-
-
-def _kmeans(Y, k, n_init=10, max_iter=300, tol=1e-4, seed=None, info=None):
-    """Seeded k-means++ initialisation + Lloyd iterations on the device; best inertia of ``n_init``
-    runs (sklearn's ``KMeans`` defaults; its relative tolerance is on the centre shift).  The Lloyd step is
-    the HIP kernel of ``csrc/kmeans.hip`` for d <= 32, k <= 64 (what PCA(n_clusters) hands over for up to 32 clusters),
-    library kernels beyond.  ``info``: a dict that receives ``iterations`` (Lloyd steps of the run kept) and ``inertia``."""
-    from ._lib import get_lib
-
-    Y = Y.contiguous()
-    n, d = Y.shape
-    if not Y.is_cuda:
-        raise RuntimeError("meld_amd needs a ROCm GPU (MI355X); there is no CPU fallback")
-    if d > 32 or k > 64:
-        # beyond what csrc/kmeans.hip stages in LDS (VertexFrequencyCluster(n_clusters > 32): PCA hands over n_clusters
-        # features): the same Lloyd step on library kernels (rocBLAS distance GEMM + index_add), any d and k
-        scratch = None
-    else:
-        nb = int(min(get_lib().meld_kmeans_max_blocks(), max(1, (n + 255) // 256)))
-        scratch = dict(nb=nb, sum=torch.empty(nb * k * d, dtype=torch.float64, device=Y.device),
-                       cnt=torch.empty(nb * k, dtype=torch.float64, device=Y.device),
-                       **{"in": torch.empty(nb, dtype=torch.float64, device=Y.device)})
-    lab = torch.empty(n, dtype=torch.int32, device=Y.device)
-    gen = torch.Generator(device=Y.device)
-    gen.manual_seed(0 if seed is None else int(seed))
-    var_tol = tol * float(Y.var(dim=0, unbiased=False).mean())
-    best = None
-    for _ in range(max(1, int(n_init))):
-        # k-means++
-        first = int(torch.randint(0, n, (1,), device=Y.device, generator=gen))
-        C = [Y[first]]
-        d2 = ((Y - C[0]) ** 2).sum(1)
-        for _c in range(1, k):
-            tot = d2.sum()
-            probs = d2 / tot if float(tot) > 0 else torch.full_like(d2, 1.0 / n)
-            nxt = int(torch.multinomial(probs, 1, generator=gen))
-            C.append(Y[nxt])
-            d2 = torch.minimum(d2, ((Y - C[-1]) ** 2).sum(1))
-        C = torch.stack(C).contiguous()
-        for _it in range(max_iter):
-            newC, _ = _lloyd_step(Y, C, lab, scratch) if scratch is not None else _lloyd_step_library(Y, C, lab)
-            shift = ((newC - C) ** 2).sum()
-            C = newC.contiguous()
-            if (_it & 7) == 7 and float(shift) <= var_tol:  # one host sync per 8 iterations
-                break
-        steps = _it + 1 if max_iter > 0 else 0
-        _, inertia = _lloyd_step(Y, C, lab, scratch) if scratch is not None else _lloyd_step_library(Y, C, lab)
-        inertia = float(inertia)
-        if best is None or inertia < best[0]:
-            best = (inertia, lab.to(torch.int64).clone(), steps)
-    if info is not None:
-        info.update(iterations=best[2], inertia=best[0])
-    return best[1]
 
 
 class VertexFrequencyCluster:
@@ -346,7 +242,7 @@ class VertexFrequencyCluster:
             return comm.all_reduce_sum(t) if comm is not None else t
 
         def gram(A, B):
-            return allsum(_tall_gram(A, B))
+            return allsum(tall_gram(A, B))
 
         lmax = float(G.lmax)
         kdiag = G.kernel_diagonal()
@@ -626,8 +522,9 @@ class VertexFrequencyCluster:
         params.update(kwargs)
         dev = self.graph.val.device
         Y = pca_project(torch.from_numpy(np.ascontiguousarray(data, dtype=np.float64)).to(dev), self.n_clusters)
-        lab = _kmeans(Y, self.n_clusters, n_init=params.get("n_init", 10), max_iter=params.get("max_iter", 300),
-                      tol=params.get("tol", 1e-4), seed=params.get("random_state", self.random_state)).cpu().numpy()
+        run = kmeans_device(Y, self.n_clusters, n_init=params.get("n_init", 10), max_iter=params.get("max_iter", 300), tol=params.get("tol", 1e-4),
+                            seed=params.get("random_state", self.random_state), seeding="k-means++", prefer="lds")
+        lab = run["labels"].to(torch.int64).cpu().numpy()
         values = self.likelihood if self.likelihood is not None else self.sample_indicator
         # scprep.utils.sort_clusters_by_values: clusters relabelled by ascending mean of the values
         values = np.asarray(values, dtype=np.float64)

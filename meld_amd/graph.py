@@ -446,8 +446,8 @@ class DeviceGraph:
         is the ``l``-th smallest label); otherwise the cells are clustered into at most ``n_landmark`` landmarks (default: the
         ``n_landmark`` the graph was fitted with) by k-means on ``diff_op @ V``, ``V`` the leading ``min(n_svd, n_landmark)`` singular
         vectors of the symmetric diffusion affinity from a seeded randomized range finder -- the same ``random_state`` gives the same labels.
-        ``kmeans``: ``"library"`` (the default: ``cluster._kmeans``) or ``"device"`` (k-means|| seeding and the Lloyd step of
-        ``csrc/kmeans_wide.hip``, ``meld_amd/kmeans.py``); part of the argument set, ValueError for any other value.
+        ``kmeans``: ``"library"`` (the default: k-means++ seeding, the LDS or library Lloyd step) or ``"device"`` (k-means|| seeding and
+        the Lloyd step of ``csrc/kmeans_wide.hip``), both in ``meld_amd/kmeans.py``; part of the argument set, ValueError for any other value.
         ValueError without ``n_landmark`` and ``clusters``, for ``n_landmark >= N`` or above ``landmark.LANDMARK_MAX``, for bad
         ``clusters`` (TypeError for a dtype that is not integer) and on a row-sharded graph.  The ``landmark_op`` property of the
         graph itself stays unimplemented: the operator lives on the record."""

@@ -145,9 +145,9 @@ def _orthonormal(Z):
     are dropped)."""
     import torch
 
-    from .cluster import _tall_gram
+    from ._device_ops import tall_gram
 
-    w, U = torch.linalg.eigh(_tall_gram(Z, Z))
+    w, U = torch.linalg.eigh(tall_gram(Z, Z))
     keep = w > 1e-12 * w[-1].clamp(min=1e-300)
     return Z @ (U[:, keep] / torch.sqrt(w[keep])[None, :])
 
@@ -158,7 +158,7 @@ def spectral_features(G, n_landmark, n_svd=100, random_state=None, info=None):
     ``default_clusters``)."""
     import torch
 
-    from .cluster import _tall_gram
+    from ._device_ops import tall_gram
     from .diffuse import diffuse_device, walk_vectors
 
     N, dev = G.N, G.val.device
@@ -177,7 +177,7 @@ def spectral_features(G, n_landmark, n_svd=100, random_state=None, info=None):
     for passes in range(1, MAX_PASSES + 1):
         Z = diff_aff(Q)
         # Rayleigh-Ritz on the current basis: the residuals of the leading n_svd Ritz pairs say when the range is found
-        T = _tall_gram(Q, Z)
+        T = tall_gram(Q, Z)
         theta, Y = torch.linalg.eigh(0.5 * (T + T.T))
         lead = torch.argsort(theta.abs(), descending=True)[:n_svd]
         R = Z @ Y[:, lead] - (Q @ Y[:, lead]) * theta[lead][None, :]
@@ -185,7 +185,7 @@ def spectral_features(G, n_landmark, n_svd=100, random_state=None, info=None):
         if (passes > POWER_ITERATIONS and residual <= RANGE_TOL) or passes == MAX_PASSES:
             break
         Q = _orthonormal(Z)
-    w, U = torch.linalg.eigh(_tall_gram(Z, Z))
+    w, U = torch.linalg.eigh(tall_gram(Z, Z))
     order = torch.argsort(w, descending=True)[:n_svd]
     order = order[w[order] > 1e-24 * w.max().clamp(min=1e-300)]
     V = Z @ (U[:, order] / torch.sqrt(w[order])[None, :])
@@ -200,7 +200,7 @@ def default_clusters(G, n_landmark, n_svd=100, random_state=None, info=None, kme
     -- k-means on ``diff_op @ V``, ``V`` the leading ``n_svd`` singular vectors of ``diff_aff = D^-1/2 K D^-1/2`` -- from existing
     kernels and library calls: ``diff_aff x = sqrt(r) * diffuse_step(x / sqrt(r))``; a seeded Gaussian ``[N, n_svd + 10]``, power
     iterations orthonormalised in between (tall Gram + small ``eigh``); ``Z = diff_aff Q``, ``Z^T Z = U S^2 U^T``, ``V = Z U S^-1``;
-    ``cluster._kmeans(diff_op V, n_landmark, n_init=1)``.  The seed is ``random_state`` (None: 0).
+    ``kmeans.kmeans_device(diff_op V, n_landmark, n_init=1)``.  The seed is ``random_state`` (None: 0).
 
     The power iterations run until the leading ``n_svd`` Ritz pairs of the basis have residuals below ``RANGE_TOL`` (4 iterations
     at least, ``MAX_PASSES`` products with ``diff_aff`` at most; one small ``eigh`` and one word read back per pass): a fixed 4 is
@@ -214,21 +214,18 @@ def default_clusters(G, n_landmark, n_svd=100, random_state=None, info=None, kme
     are the best partition by 1.5 %, and neither this k-means nor sklearn's finds it from a k-means++ start), while on four
     columns every start does.  Upstream's default (2,000 landmarks, 100 vectors) is not touched by the clip.
 
-    ``kmeans="device"`` clusters the same features with ``kmeans.kmeans_device`` (k-means|| seeding, the Lloyd step of
-    ``csrc/kmeans_wide.hip``) under the same seed and iteration cap; ``"library"`` is ``cluster._kmeans``, as before."""
+    ``kmeans="library"`` seeds with k-means++ and prefers the LDS Lloyd step (``csrc/kmeans.hip``; the library step beyond what it
+    stages); ``"device"`` clusters the same features with k-means|| seeding and the Lloyd step of ``csrc/kmeans_wide.hip`` under the
+    same seed and iteration cap."""
     import torch
+
+    from .kmeans import kmeans_device
 
     features = spectral_features(G, n_landmark, n_svd=n_svd, random_state=random_state, info=info)
     km = {}
     seed = 0 if random_state is None else int(random_state)
-    if kmeans == "device":
-        from .kmeans import kmeans_device
-
-        lab = kmeans_device(features, int(n_landmark), n_init=1, max_iter=KMEANS_MAX_ITER, seed=seed, info=km)["labels"].to(torch.int64)
-    else:
-        from .cluster import _kmeans
-
-        lab = _kmeans(features, int(n_landmark), n_init=1, max_iter=KMEANS_MAX_ITER, seed=seed, info=km)
+    route = dict(seeding="k-means||", prefer="wide") if kmeans == "device" else dict(seeding="k-means++", prefer="lds")
+    lab = kmeans_device(features, int(n_landmark), n_init=1, max_iter=KMEANS_MAX_ITER, seed=seed, info=km, **route)["labels"].to(torch.int64)
     if G.perm is not None:  # (device row v is the caller's cell perm[v])
         out = torch.empty_like(lab)
         out[G.perm] = lab
@@ -340,7 +337,8 @@ def _build(G, compact, L, info):
 
 
 def check_kmeans(kmeans):
-    """``kmeans`` as one of ``"library"`` (``cluster._kmeans``) and ``"device"`` (``kmeans.kmeans_device``); ValueError otherwise."""
+    """``kmeans`` as one of the two routes of ``kmeans.kmeans_device``, ``"library"`` (k-means++, the LDS or library step) and
+    ``"device"`` (k-means||, the wide step); ValueError otherwise."""
     if not isinstance(kmeans, str) or kmeans not in ("library", "device"):
         raise ValueError("kmeans must be 'library' or 'device', got {!r}".format(kmeans))
     return kmeans

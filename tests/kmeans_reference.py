@@ -145,6 +145,16 @@ def blobs(n_blobs=80, per=50, d=10, spacing=40.0, seed=5):
     return X[order], truth[order]
 
 
+def step_case(n=1001, d=7, seed=41):
+    """``(Y, C)`` for the Lloyd steps side by side: ``n`` points (no multiple of a workgroup's 256) in four unit Gaussians 8 apart,
+    five centres -- the blobs' displaced by a unit Gaussian, and one at 50 in every coordinate that no point is nearest to."""
+    rng = np.random.default_rng(seed)
+    means = 8.0 * np.eye(4, d)
+    Y = rng.standard_normal((n, d)) + means[rng.integers(0, 4, n)]
+    C = np.concatenate([means + rng.standard_normal((4, d)), np.full((1, d), 50.0)])
+    return Y, C
+
+
 def overlapping_blobs(n=4000, d=20, k=100, spacing=3.0, seed=6):
     rng = np.random.default_rng(seed)
     centres = spacing * rng.integers(0, 4, size=(k, d)).astype(np.float64)

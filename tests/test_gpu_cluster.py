@@ -156,17 +156,15 @@ def test_filterbank_clusters_like_the_reference_on_clear_structure():
 
 def test_kmeans_kernel_equals_a_plain_lloyd_step():
     import torch
-    from meld_amd.cluster import _kmeans, _lloyd_step
-    from meld_amd._lib import get_lib
+    from meld_amd.kmeans import kmeans_device, lds_step, library_step
+
+    def _kmeans(Y, k, **kw):  # (the route VertexFrequencyCluster.predict takes)
+        return kmeans_device(Y, k, seeding="k-means++", prefer="lds", **kw)["labels"].to(torch.int64)
 
     rng = np.random.default_rng(2)
     Y = torch.from_numpy(rng.normal(size=(70_001, 7))).cuda()
     C = Y[:5].clone().contiguous()
-    nb = 64
-    scratch = dict(nb=nb, sum=torch.empty(nb * 5 * 7, dtype=torch.float64, device="cuda"), cnt=torch.empty(nb * 5, dtype=torch.float64, device="cuda"),
-                   **{"in": torch.empty(nb, dtype=torch.float64, device="cuda")})
-    lab = torch.empty(70_001, dtype=torch.int32, device="cuda")
-    newC, inertia = _lloyd_step(Y, C, lab, scratch)
+    newC, inertia, lab = lds_step(Y, 5)(Y, C)
     D = torch.cdist(Y, C) ** 2
     ref_lab = D.argmin(1)
     assert torch.equal(lab.to(torch.int64), ref_lab)
@@ -176,10 +174,7 @@ def test_kmeans_kernel_equals_a_plain_lloyd_step():
     out = _kmeans(Y, 4, n_init=2, seed=1)
     assert out.shape == (70_001,) and set(out.unique().tolist()) == {0, 1, 2, 3}
     # beyond the kernel's LDS staging (d > 32 or k > 64): the library Lloyd step, same outputs
-    from meld_amd.cluster import _lloyd_step_library
-
-    lab2 = torch.empty_like(lab)
-    newC2, inertia2 = _lloyd_step_library(Y, C, lab2)
+    newC2, inertia2, lab2 = library_step(Y, C)
     assert torch.equal(lab2, lab) and torch.allclose(newC2, newC, rtol=1e-12, atol=1e-12)
     assert abs(float(inertia2) - float(inertia)) <= 1e-9 * float(inertia)
     Yw = torch.from_numpy(rng.normal(size=(5000, 40)) + 6.0 * rng.integers(0, 2, size=(5000, 1))).cuda()

@@ -216,19 +216,82 @@ def test_kmeans_wider_than_the_kernel_runs_on_the_library():
     assert np.array_equal(km.predict(X), km.labels_)
 
 
+def _steps(Yd, k):
+    from meld_amd import kmeans
+
+    return {"lds": kmeans.lds_step(Yd, k), "wide": kmeans.lloyd_step, "library": kmeans.library_step}
+
+
+def test_the_three_back_ends_agree_on_one_step():
+    """One step of every back end through the common signature on 1,001 points (no multiple of 256), d = 7, k = 5, one centre that
+    no point is nearest to.  No point of the case is within ``2 tau`` of a tie (tests/test_kmeans_reference.py), so every label
+    is compared.  Centres: 1e-12, the bound tests/test_gpu_cluster.py holds the LDS and library steps to; inertia: 1e-9 relative."""
+    Y, C = ref.step_case()
+    want = ref.argmin_lowest(ref.distances(Y, C))
+    Yd, Cd = _dev(Y), _dev(C)
+    out = {name: step(Yd, Cd) for name, step in _steps(Yd, 5).items()}
+    newC, inertia, lab = out["wide"]
+    for name, (newC_b, inertia_b, lab_b) in out.items():
+        print(name, "largest centre difference to wide", float((newC_b - newC).abs().max()), "inertia", float(inertia_b))
+        assert lab_b.dtype == torch.int32 and np.array_equal(lab_b.cpu().numpy(), want), name
+        assert torch.allclose(newC_b, newC, rtol=1e-12, atol=1e-12), name
+        assert torch.equal(newC_b[4], Cd[4]), name  # (the empty cluster keeps its centre, bit for bit)
+        assert abs(float(inertia_b) - float(inertia)) <= 1e-9 * float(inertia), name
+    np.testing.assert_allclose(newC.cpu().numpy(), ref.lloyd_step(Y, C)[1].astype(np.float64), rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize("backend", ["lds", "wide", "library"])
+def test_lloyd_over_every_step(backend):
+    """``lloyd`` with ``max_iter`` 0, 1 and 20 on the case above: the step count follows ``max_iter`` and the stopping rule (looked
+    at after steps 8 and 16 only; the plain loop below says where it holds), the history has one entry per step, the labels and the
+    inertia are those of the returned centres; the wide back end gives the same bits twice."""
+    from meld_amd.kmeans import CHECK_EVERY, lloyd, lloyd_step
+
+    Y, C = ref.step_case()
+    Yd, Cd = _dev(Y), _dev(C)
+    step = _steps(Yd, 5)[backend]
+    var_tol = 1e-4 * float(np.var(Y, axis=0).mean())
+    Cs, expected = Cd, {0: 0, 1: 1, 20: 20}
+    for it in range(20):
+        newC = lloyd_step(Yd, Cs)[0]
+        shift, Cs = float(((newC - Cs) ** 2).sum()), newC
+        if it % CHECK_EVERY == CHECK_EVERY - 1:
+            assert not 0.5 * var_tol < shift < 2.0 * var_tol  # (far from the threshold: rounding cannot move the stop)
+            if shift <= var_tol:
+                expected[20] = it + 1
+                break
+    assert expected[20] == 8  # (four separate blobs: settled long before the first look)
+    for max_iter, steps in expected.items():
+        run = lloyd(Yd, Cd, step, max_iter=max_iter, tol=1e-4)
+        centres = run["centres"].cpu().numpy()
+        assert run["iterations"] == steps and tuple(run["history"].shape) == (steps,) and run["history"].dtype == torch.float64
+        assert int((ref.gaps(ref.distances(Y, centres)) <= 2 * ref.tau(Y, centres)).sum()) == 0
+        assert run["labels"].dtype == torch.int32
+        assert np.array_equal(run["labels"].cpu().numpy(), ref.argmin_lowest(ref.distances(Y, centres)))
+        want = float(ref.inertia(Y, centres))
+        assert abs(run["inertia"] - want) <= 1e-9 * want
+        assert np.array_equal(centres[4], C[4])
+        if max_iter == 0:
+            assert np.array_equal(centres, C)
+        if backend == "wide":
+            again = lloyd(Yd, Cd, step, max_iter=max_iter, tol=1e-4)
+            assert torch.equal(again["centres"], run["centres"]) and torch.equal(again["labels"], run["labels"])
+            assert torch.equal(again["history"], run["history"]) and again["inertia"] == run["inertia"]
+
+
 @pytest.mark.parametrize("which", ["overlapping", "uniform"])
 def test_quality_against_the_parent_kmeans(which):
-    """The yardstick is ``cluster._kmeans`` (k-means++ seeding, the library Lloyd step) with seeds 0-4: the device route with seed 0
-    may not exceed its worst inertia by more than its own spread over the seeds."""
+    """The yardstick is the parent route, ``kmeans_device`` with k-means++ seeding and the LDS step preferred (here: the library Lloyd
+    step), with seeds 0-4: the device route with seed 0 may not exceed its worst inertia by more than its own spread over the seeds."""
     from meld_amd import KMeans
-    from meld_amd.cluster import _kmeans
+    from meld_amd.kmeans import kmeans_device
 
     X = ref.overlapping_blobs() if which == "overlapping" else ref.uniform_noise()
     Xd = _dev(X)
     parent = []
     for seed in range(5):
         info = {}
-        _kmeans(Xd, 100, n_init=1, max_iter=300, tol=1e-4, seed=seed, info=info)
+        kmeans_device(Xd, 100, n_init=1, max_iter=300, tol=1e-4, seed=seed, info=info, seeding="k-means++", prefer="lds")
         parent.append(info["inertia"])
     km = KMeans(100, random_state=0).fit(Xd)
     print("quality[{}]: parent min {:.6g} max {:.6g}, device {:.6g}, device / parent max {:.5f}, device / parent min {:.5f}".format(
@@ -245,14 +308,14 @@ def cells():
 
 
 def test_landmarks_by_the_device_route(cells, monkeypatch):
-    import meld_amd.cluster
+    import meld_amd.kmeans
 
     def not_this_one(*a, **kw):
-        raise AssertionError("kmeans='device' must not run cluster._kmeans")
+        raise AssertionError("kmeans='device' must not run the k-means++ seeder")
 
     G = cells.graph
     with monkeypatch.context() as m:
-        m.setattr(meld_amd.cluster, "_kmeans", not_this_one)
+        m.setattr(meld_amd.kmeans, "seed_plusplus", not_this_one)
         lm = G.landmarks(200, random_state=1, kmeans="device")
         with pytest.raises(AssertionError, match="must not run"):  # (and the default route does run it)
             G.landmarks(199, random_state=1)

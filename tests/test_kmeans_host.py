@@ -133,3 +133,26 @@ def test_wide_kmeans_kernels_do_not_spill():
     assert len(kernels) == 10 and sum("kmeans_wide_assign_kernel" in k for k in kernels) == 8, sorted(rows)
     for name, r in kernels.items():
         assert r["ScratchSize [bytes/lane]:"] == 0, (name, r)
+
+
+@pytest.mark.parametrize("d, k, prefer, expected", [
+    (32, 64, "lds", "lds"), (33, 64, "lds", "library"), (32, 65, "lds", "library"), (1, 1, "lds", "lds"),
+    (128, 1, "wide", "wide"), (128, 5000, "wide", "wide"), (129, 1, "wide", "library"), (129, 5000, "wide", "library"),
+])
+def test_the_back_end_a_shape_takes(d, k, prefer, expected):
+    from meld_amd.kmeans import pick_backend
+
+    assert pick_backend(d, k, prefer) == expected
+    with pytest.raises(ValueError, match="prefer must be"):
+        pick_backend(d, k, "device")
+
+
+def test_kmeans_imports_without_the_vfc_module():
+    """k-means lives in ``meld_amd.kmeans`` alone: importing it, and ``meld_amd.landmark`` that calls it, does not import
+    ``meld_amd.cluster`` (checked in a fresh interpreter)."""
+    import subprocess
+    import sys
+
+    code = "import sys, meld_amd.kmeans, meld_amd.landmark; assert 'meld_amd.cluster' not in sys.modules, 'cluster imported'"
+    out = subprocess.run([sys.executable, "-c", code], cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+    assert out.returncode == 0, out.stdout

@@ -65,6 +65,15 @@ def test_duplicate_case_is_what_it_says():
     assert int((ref.gaps(D2) <= 2 * ref.tau(Y, C)).sum()) == 0
 
 
+def test_step_case_decides_every_point_and_leaves_one_cluster_empty():
+    Y, C = ref.step_case()
+    assert Y.shape == (1001, 7) and C.shape == (5, 7)
+    D = ref.distances(Y, C)
+    assert int((ref.gaps(D) <= 2 * ref.tau(Y, C)).sum()) == 0  # (no row is left out of a label comparison)
+    lab, newC, _ = ref.lloyd_step(Y, C)
+    assert np.bincount(lab, minlength=5)[:4].min() > 100 and not (lab == 4).any() and np.array_equal(newC[4], C[4])
+
+
 def test_blobs_are_separate():
     X, truth = ref.blobs()
     assert X.shape == (4000, 10) and np.bincount(truth).tolist() == [50] * 80

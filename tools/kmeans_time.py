@@ -1,16 +1,16 @@
 """k-means with thousands of centres (meld_amd/kmeans.py, csrc/kmeans_wide.hip) against the route that existed before it
-(cluster._kmeans: a sequential k-means++ and cluster._lloyd_step_library), in one run:
+(``kmeans_device`` with a sequential k-means++ and the LDS step preferred, here ``library_step``), in one run:
 
     python tools/kmeans_time.py [--shapes 1000000x100x2000,1000000x50x2000,100000x100x4096] [--landmarks-n 1000000] [--landmarks 2000]
                                 [--reps 10] [--out FILE] [--label TEXT]
 
 Per shape n x d x k (a seeded mixture of k Gaussians on the device, the starting centres k of its rows):
-  (a) one Lloyd step through ``_lloyd_step_library`` and through ``kmeans.lloyd_step``, the two alternating, device events around each
+  (a) one Lloyd step through ``kmeans.library_step`` and through ``kmeans.lloyd_step``, the two alternating, device events around each
       call after two untimed calls of each; the device step's assign, sort + counts and sums launches apart; the two routes' labels
       and centres compared;
-  (b) both seedings: ``_kmeans(max_iter=0)`` (k-means++: k passes, a read-back in each, then one library step) and
-      ``kmeans_device(max_iter=0)`` (k-means||, then one assign), wall clocks around synchronised calls, with the inertia each
-      seeding starts Lloyd from.
+  (b) both seedings: ``kmeans_device(max_iter=0, seeding="k-means++", prefer="lds")`` (k passes, a read-back in each, then one
+      library step) and ``kmeans_device(max_iter=0)`` (k-means||, then one assign), wall clocks around synchronised calls, with the
+      inertia each seeding starts Lloyd from.
 Then, on MELD(knn=5).fit(bench.synthetic_cells(N, 50, seed 0)): (c) ``spectral_features`` once and both k-means on them, (d) whole
 ``landmarks(L, recompute=True)`` by both routes (wall clocks).
 The baseline of every ratio is the library route measured in this run.  Clocks are not pinned; every figure is of this run."""
@@ -27,7 +27,12 @@ import torch
 
 import meld_amd
 from meld_amd import kmeans as km
-from meld_amd.cluster import _kmeans, _lloyd_step_library
+
+
+def _kmeans(Y, k, **kw):
+    """the library route: sequential k-means++, the LDS step preferred (beyond what it stages: ``library_step``)"""
+    return km.kmeans_device(Y, k, seeding="k-means++", prefer="lds", **kw)["labels"].to(torch.int64)
+
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--shapes", default="1000000x100x2000,1000000x50x2000,100000x100x4096")
@@ -110,17 +115,16 @@ for shape in [s for s in args.shapes.split(",") if s]:
     gen = torch.Generator(device="cuda")
     gen.manual_seed(1)
     C = Y[torch.randperm(n, device="cuda", generator=gen)[:k]].contiguous()
-    lab_lib = torch.empty(n, dtype=torch.int32, device="cuda")
     say("--- n {} d {} k {}".format(n, d, k))
     lab_dev, _ = km.assign(Y, C)
     t = alternating({
-        "library": lambda: _lloyd_step_library(Y, C, lab_lib),
+        "library": lambda: km.library_step(Y, C),
         "device": lambda: km.lloyd_step(Y, C),
         "assign": lambda: km.assign(Y, C),
         "sort": lambda: (torch.sort(lab_dev, stable=True), torch.bincount(lab_dev, minlength=k)),
         "sort+sums": lambda: km.segment_sums(Y, lab_dev, k),
     })
-    newC_lib, in_lib = _lloyd_step_library(Y, C, lab_lib)
+    newC_lib, in_lib, lab_lib = km.library_step(Y, C)
     newC_dev, in_dev, lab_dev = km.lloyd_step(Y, C)
     flops = 2.0 * n * k * d
     say("(a) Lloyd step: library {} | device {} | device / library {:.3f}".format(fmt(t["library"]), fmt(t["device"]), t["device"][0] / t["library"][0]))
@@ -132,7 +136,7 @@ for shape in [s for s in args.shapes.split(",") if s]:
     _, t_lib = wall(lambda: _kmeans(Y, k, n_init=1, max_iter=0, seed=0, info=info_lib))
     km.kmeans_device(Y, k, n_init=1, max_iter=0, seed=1)  # (untimed: the shapes of the seeding's library calls)
     run, t_dev = wall(lambda: km.kmeans_device(Y, k, n_init=1, max_iter=0, seed=0, info=info_dev))
-    say("(b) seeding + one assignment: k-means++ of _kmeans {:.3f} s (inertia {:.6g}) | k-means|| {:.3f} s (inertia {:.6g}, {} candidates) | "
+    say("(b) seeding + one assignment: k-means++ {:.3f} s (inertia {:.6g}) | k-means|| {:.3f} s (inertia {:.6g}, {} candidates) | "
         "device / library {:.4f}".format(t_lib, info_lib["inertia"], t_dev, info_dev["inertia"], run.get("seed_candidates"), t_dev / t_lib))
     del Y, C
     torch.cuda.empty_cache()

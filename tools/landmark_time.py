@@ -90,11 +90,12 @@ def stages(G, label_dev, L):
 
 def clustering(G, n_landmark):
     """the default clustering with its two stages timed apart (landmark.default_clusters is the two in a row)"""
-    from meld_amd.cluster import _kmeans
+    from meld_amd.kmeans import kmeans_device
 
     info, km = {}, {}
     feats, t_feat = wall(lambda: landmark.spectral_features(G, n_landmark, n_svd=100, random_state=0, info=info))
-    lab, t_km = wall(lambda: _kmeans(feats, n_landmark, n_init=1, max_iter=landmark.KMEANS_MAX_ITER, seed=0, info=km))
+    lab, t_km = wall(lambda: kmeans_device(feats, n_landmark, n_init=1, max_iter=landmark.KMEANS_MAX_ITER, seed=0, info=km,
+                                           seeding="k-means++", prefer="lds")["labels"].to(torch.int64))
     info.update(kmeans_iterations=km.get("iterations"), seconds_features=t_feat, seconds_kmeans=t_km)
     if G.perm is not None:
         out = torch.empty_like(lab)

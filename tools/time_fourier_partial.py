@@ -7,7 +7,7 @@ Data: oracle.synthetic_cells(n, n_dims=d), graph by MELD(knn).fit.  Reports JSON
 1. per k: wall time of ``fourier_basis_device(k, recompute=True)`` (host clock around device synchronisations, median / min / max of
    ``--reps`` runs after a warm-up), the outer iterations and filter degrees, and the per-stage split from the library's own
    ``_EventSpan`` timers (device events; medians over the same runs): filter (every wide step), Gram, rotate, residuals;
-2. each block operation at [n, 64] against the library route it replaces -- Gram: chunked ``torch.bmm`` (``cluster._tall_gram``);
+2. each block operation at [n, 64] against the library route it replaces -- Gram: chunked ``torch.bmm`` (``_device_ops.tall_gram``);
    rotate: ``V @ S``; orthonormalisation (2 x (Gram + host eigh + rotate)): ``torch.linalg.qr``; residuals: the tensor expression --
    the two routes in turn, one sample = ``--inner`` calls between two device events, median and quartiles of ``--block-reps`` samples;
 3. with ``--host-n`` > 0: ``scipy.sparse.linalg.eigsh`` in shift-invert mode on a graph of that many cells (the comparison pygsp
@@ -83,7 +83,7 @@ def time_basis(G, k, reps):
 
 
 def time_blocks(G, reps, inner):
-    from meld_amd.cluster import _tall_gram
+    from meld_amd._device_ops import tall_gram
     from meld_amd.filter import _ops_of
     from meld_amd.spectrum import orthonormaliser
 
@@ -105,7 +105,7 @@ def time_blocks(G, reps, inner):
             ops.block_rotate(out, Sd, n, m, out)
 
     pairs = dict(
-        gram=(lambda: ops.block_gram(V, W, n, m, part, nb, C), lambda: _tall_gram(V, W)),
+        gram=(lambda: ops.block_gram(V, W, n, m, part, nb, C), lambda: tall_gram(V, W)),
         rotate=(lambda: ops.block_rotate(V, S, n, m, out), lambda: torch.matmul(V, S, out=out)),
         residuals=(lambda: ops.block_residuals(W, V, theta, n, m, part, nb, res), lambda: ((W - theta[None, :] * V) ** 2).sum(0)),
         orthonormalise=(ortho_hip, lambda: torch.linalg.qr(V)),
