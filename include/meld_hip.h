@@ -1165,9 +1165,27 @@ int meld_ranksum_scan(const uint64_t* keys_sorted, const uint64_t* payload_sorte
  *   rescale still multiplies: sklearn's normalize), then out_val = f(w) for transform MELD_PREP_IDENTITY w, _SQRT sqrt(w), _LOG
  *   log(w + 1), _LOG2 log2(w + 1), _LOG10 log10(w + 1), _ARCSINH asinh(w / cofactor).  out_val_norm (NULL: not wanted) receives w.
  *
- * Each entry returns -1 before any launch, naming itself, for a NULL required pointer, val_f32 outside {0, 1}, n_rows, n_cols or
- * n_keep outside [1, 2^31), a transform outside [0, 5], a cofactor <= 0 with MELD_PREP_ARCSINH. */
+ * meld_prep_gene_moments: per-gene count, mean and variance over the kept cells, on the CSR of X^T (one row per gene, as the
+ *   rank-sum entries take it: rowptr[n_genes + 1], col = cell indices in [0, n_cells)).  row_keep (uint8 [n_cells]; NULL: every
+ *   cell), n_kept = the number of kept cells (the caller knows it), gene_mask (uint8 [n_genes]; NULL: every gene), ddof 0 or 1.
+ *   The value of a stored entry v of a kept cell i is the rewrite's, same operations in the same order:  w = row_scale ?
+ *   (v / row_scale[i]) * rescale : v  (row_scale fp64 [n_cells], indexed by the INPUT's cell; a cell with row_scale[i] == 0 keeps v,
+ *   rescale still multiplies), x = f(w).  Implicit zeros and the entries of cells that are not kept contribute nothing (f(0) = 0).
+ *     count[g] (int32) = the stored entries of kept cells;  mean[g] = (sum of x) / n_kept;
+ *     var[g] = (sum over those entries of (x - mean)^2 + (n_kept - count) * mean^2) / (n_kept - ddof)   -- two passes over the gene.
+ *   A gene with gene_mask[g] == 0 gets count = -1, mean = var = 0 and its entries are not read.
+ *   Order of the sums: number the gene's STORED entries 0, 1, 2 ... (an entry that is not counted stands in its place as +0.0).  A
+ *   gene of at most MELD_PREP_MOMENTS_WAVE_MAX stored entries: lane l of one wave adds the entries l, l + 64, ... in that order,
+ *   then a fixed butterfly over the 64 lanes.  A longer gene: thread t of a workgroup of MELD_PREP_MOMENTS_THREADS adds the entries
+ *   t, t + 1024, ... in that order, the same butterfly in each of the 16 waves, then a fixed pairwise tree over the 16 wave sums.
+ *   Either way a function of the gene's stored length alone: not of the grid, not of what else ran.  Two calls give the same bits.
+ *
+ * Each entry returns -1 before any launch, naming itself, for a NULL required pointer, val_f32 outside {0, 1}, n_rows, n_cols,
+ * n_genes, n_cells or n_keep outside [1, 2^31), a transform outside [0, 5], a cofactor <= 0 with MELD_PREP_ARCSINH; the moments
+ * also for ddof outside {0, 1}, n_kept < 1 and n_kept - ddof < 1. */
 #define MELD_PREP_PANEL_COLS 32768
+#define MELD_PREP_MOMENTS_WAVE_MAX 2048 /* stored entries of a gene up to which one wave takes it; above, a workgroup */
+#define MELD_PREP_MOMENTS_THREADS 1024
 #define MELD_PREP_IDENTITY 0
 #define MELD_PREP_SQRT 1
 #define MELD_PREP_LOG 2
@@ -1185,6 +1203,10 @@ int meld_prep_select_fill(const int64_t* rowptr, const int32_t* col, const void*
                           const int32_t* rows, int64_t n_keep, const int32_t* col_map, const double* scale, double rescale,
                           int transform, double cofactor, const int64_t* out_rowptr, int32_t* out_col, double* out_val,
                           double* out_val_norm, meld_stream_t stream);
+int meld_prep_gene_moments(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t n_genes, int64_t n_cells,
+                           const uint8_t* row_keep, const double* row_scale, double rescale, int transform, double cofactor,
+                           const uint8_t* gene_mask, int64_t n_kept, int ddof, int32_t* count, double* mean, double* var,
+                           meld_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -228,6 +228,7 @@ SIGNATURES = {
     "meld_prep_col_counts": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _ptr, _f64, _ptr, _ptr]),
     "meld_prep_select_count": (_i32, [_ptr, _ptr, _i64, _i64, _ptr, _i64, _ptr, _ptr, _ptr]),
     "meld_prep_select_fill": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _ptr, _i64, _ptr, _ptr, _f64, _i32, _f64, _ptr, _ptr, _ptr, _ptr, _ptr]),
+    "meld_prep_gene_moments": (_i32, [_ptr, _ptr, _ptr, _i32, _i64, _i64, _ptr, _ptr, _f64, _i32, _f64, _ptr, _i64, _i32, _ptr, _ptr, _ptr, _ptr]),
 }
 
 

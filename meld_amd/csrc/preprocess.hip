@@ -273,6 +273,162 @@ __global__ __launch_bounds__(PREP_THREADS) void select_fill_kernel(const long lo
   }
 }
 
+// ---- per-gene count, mean and two-pass variance on the gene-major copy (the CSR of X^T) ---------------------------------------------
+// ORDER OF A GENE'S SUMS: number the gene's STORED entries 0, 1, 2 ...; an entry that is not counted (its cell is not kept, or its
+// index lies outside the matrix) stands in its place as +0.0.  Up to MELD_PREP_MOMENTS_WAVE_MAX entries one wave takes the gene:
+// lane l adds the entries l, l + 64, ... in that order, then the fixed butterfly.  A longer gene takes the workgroup: thread t adds
+// the entries t, t + 1024, ..., the butterfly in each wave, a fixed pairwise tree over the 16 wave sums in LDS.  mom_pass is the one
+// loop of both routes and both passes (the stride is 64 or 1024); the route is a function of the stored length, so the order is.
+// A workgroup owns 16 consecutive genes: each wave does its own if it is short, then all of them walk the long ones together.
+constexpr int MOM_THREADS = MELD_PREP_MOMENTS_THREADS;
+constexpr int MOM_WAVES = MOM_THREADS / WAVE;
+constexpr int MOM_WAVE_MAX = MELD_PREP_MOMENTS_WAVE_MAX;
+static_assert(MOM_WAVES == 16, "the tree of mom_tree is written for 16 wave sums");
+
+struct MomOperand {
+  const int* col;
+  const void* val;
+  int n_cells;
+  const unsigned char* row_keep;
+  const double* row_scale;
+  double rescale;
+  int code;
+  double cofactor;
+};
+
+// every load of an entry, none of them conditional (four entries' loads go out together): a cell index outside the matrix reads
+// the per-cell vectors at 0 and is not counted
+template <bool F32>
+__device__ __forceinline__ void mom_fetch(const MomOperand& a, long long e, double& v, double& s, bool& keep) {
+  const int c = a.col[e];
+  v = prep_load<F32>(a.val, e);
+  const bool ok = (unsigned)c < (unsigned)a.n_cells;
+  const int ci = ok ? c : 0;
+  keep = ok && (!a.row_keep || a.row_keep[ci] != 0);
+  s = a.row_scale ? a.row_scale[ci] : 1.0;
+}
+
+// the value of select_fill_kernel, operation by operation
+__device__ __forceinline__ double mom_value(const MomOperand& a, double v, double s, bool keep) {
+  if (!keep) return 0.0;
+  const double wv = a.row_scale ? (s == 0.0 ? v : v / s) * a.rescale : v;
+  return prep_transform(wv, a.code, a.cofactor);
+}
+
+template <bool SECOND>
+__device__ __forceinline__ void mom_add(double x, bool keep, double mean, double& acc, int& cnt) {
+  if (SECOND) {
+    const double d = keep ? x - mean : 0.0;
+    acc += d * d;
+  } else {
+    acc += x;
+    cnt += keep;
+  }
+}
+
+// first pass: acc += x, cnt += counted; second: acc += (x - mean)^2 over the counted entries.  e: this thread's first entry.
+template <bool F32, bool SECOND>
+__device__ __forceinline__ void mom_pass(const MomOperand& a, long long e, long long e1, int stride, double mean, double& acc, int& cnt) {
+  for (; e + 3ll * stride < e1; e += 4ll * stride) {  // four entries in flight, added in storage order
+    double v[4], s[4];
+    bool keep[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) mom_fetch<F32>(a, e + (long long)u * stride, v[u], s[u], keep[u]);
+#pragma unroll
+    for (int u = 0; u < 4; ++u) mom_add<SECOND>(mom_value(a, v[u], s[u], keep[u]), keep[u], mean, acc, cnt);
+  }
+  for (; e < e1; e += stride) {
+    double v, s;
+    bool keep;
+    mom_fetch<F32>(a, e, v, s, keep);
+    mom_add<SECOND>(mom_value(a, v, s, keep), keep, mean, acc, cnt);
+  }
+}
+
+__device__ __forceinline__ double mom_tree(const double* part) {  // ((p0 + p8) + (p4 + p12)) + ... : the same in every thread
+  double p[MOM_WAVES];
+#pragma unroll
+  for (int i = 0; i < MOM_WAVES; ++i) p[i] = part[i];
+#pragma unroll
+  for (int half = MOM_WAVES / 2; half > 0; half >>= 1)
+#pragma unroll
+    for (int i = 0; i < half; ++i) p[i] += p[i + half];
+  return p[0];
+}
+
+__device__ __forceinline__ void mom_store(long long g, int c, double m, double ss, long long n_kept, int ddof, int* __restrict__ count,
+                                          double* __restrict__ mean, double* __restrict__ var) {
+  count[g] = c;
+  mean[g] = m;
+  var[g] = (ss + (double)(n_kept - c) * (m * m)) / (double)(n_kept - ddof);
+}
+
+template <bool F32>
+__global__ __launch_bounds__(MOM_THREADS) void gene_moments_kernel(const long long* __restrict__ rowptr, MomOperand a, long long n_genes,
+                                                                   const unsigned char* __restrict__ gene_mask, long long n_kept, int ddof,
+                                                                   int* __restrict__ count, double* __restrict__ mean,
+                                                                   double* __restrict__ var) {
+  __shared__ double s_part[MOM_WAVES];
+  __shared__ int s_cnt[MOM_WAVES];
+  const int lane = lane_id();
+  const int w = threadIdx.x / WAVE;
+  const long long g0 = (long long)blockIdx.x * MOM_WAVES;
+  const double nk = (double)n_kept;
+  {  // a wave per gene: masked genes and short ones (no wave leaves: barriers follow)
+    const long long g = g0 + w;
+    if (g < n_genes) {
+      if (gene_mask && gene_mask[g] == 0) {
+        if (lane == 0) {
+          count[g] = -1;
+          mean[g] = 0.0;
+          var[g] = 0.0;
+        }
+      } else {
+        const long long e0 = rowptr[g], e1 = rowptr[g + 1];
+        if (e1 - e0 <= MOM_WAVE_MAX) {
+          double s = 0.0, ss = 0.0;
+          int c = 0, unused = 0;
+          mom_pass<F32, false>(a, e0 + lane, e1, WAVE, 0.0, s, c);
+          s = wave_sum(s);
+          c = wave_sum_i32(c);
+          const double m = s / nk;
+          mom_pass<F32, true>(a, e0 + lane, e1, WAVE, m, ss, unused);
+          ss = wave_sum(ss);
+          if (lane == 0) mom_store(g, c, m, ss, n_kept, ddof, count, mean, var);
+        }
+      }
+    }
+  }
+  for (int j = 0; j < MOM_WAVES; ++j) {  // the long genes of the 16, the whole workgroup on each (every branch here is uniform)
+    const long long g = g0 + j;
+    if (g >= n_genes) break;
+    if (gene_mask && gene_mask[g] == 0) continue;
+    const long long e0 = rowptr[g], e1 = rowptr[g + 1];
+    if (e1 - e0 <= MOM_WAVE_MAX) continue;
+    double s = 0.0, ss = 0.0;
+    int c = 0, unused = 0;
+    mom_pass<F32, false>(a, e0 + threadIdx.x, e1, MOM_THREADS, 0.0, s, c);
+    s = wave_sum(s);
+    c = wave_sum_i32(c);
+    if (lane == 0) {
+      s_part[w] = s;
+      s_cnt[w] = c;
+    }
+    __syncthreads();
+    const double m = mom_tree(s_part) / nk;
+    c = 0;
+#pragma unroll
+    for (int i = 0; i < MOM_WAVES; ++i) c += s_cnt[i];
+    __syncthreads();  // every thread has read the sums before the second pass writes its own
+    mom_pass<F32, true>(a, e0 + threadIdx.x, e1, MOM_THREADS, m, ss, unused);
+    ss = wave_sum(ss);
+    if (lane == 0) s_part[w] = ss;
+    __syncthreads();
+    if (threadIdx.x == 0) mom_store(g, c, m, mom_tree(s_part), n_kept, ddof, count, mean, var);
+    __syncthreads();  // ... and thread 0 before the next gene's
+  }
+}
+
 }  // namespace meld
 
 using namespace meld;
@@ -373,5 +529,30 @@ extern "C" int meld_prep_select_fill(const int64_t* rowptr, const int32_t* col, 
     select_fill_kernel<false><<<prep_row_blocks(n_keep), PREP_THREADS, 0, S(stream)>>>(rp, col, val, n_rows, (int)n_cols, rows, n_keep, col_map, scale,
                                                                                       rescale, transform, cofactor, orp, out_col, out_val, out_val_norm);
   MELD_LAUNCH_CHECK("select_fill_kernel");
+  return MELD_OK;
+}
+
+extern "C" int meld_prep_gene_moments(const int64_t* rowptr, const int32_t* col, const void* val, int val_f32, int64_t n_genes,
+                                      int64_t n_cells, const uint8_t* row_keep, const double* row_scale, double rescale, int transform,
+                                      double cofactor, const uint8_t* gene_mask, int64_t n_kept, int ddof, int32_t* count, double* mean,
+                                      double* var, meld_stream_t stream) {
+  MELD_CHECK_ARG(rowptr && col && val && count && mean && var, "meld_prep_gene_moments: rowptr, col, val, count, mean and var are required");
+  MELD_CHECK_ARG(val_f32 == 0 || val_f32 == 1, "meld_prep_gene_moments: val_f32=%d outside {0, 1}", val_f32);
+  MELD_CHECK_ARG(n_genes > 0 && n_genes < (1ll << 31), "meld_prep_gene_moments: n_genes=%lld outside [1, 2^31)", (long long)n_genes);
+  MELD_CHECK_ARG(n_cells > 0 && n_cells < (1ll << 31), "meld_prep_gene_moments: n_cells=%lld outside [1, 2^31)", (long long)n_cells);
+  MELD_CHECK_ARG(transform >= MELD_PREP_IDENTITY && transform <= MELD_PREP_ARCSINH, "meld_prep_gene_moments: transform=%d outside [0, 5]", transform);
+  MELD_CHECK_ARG(transform != MELD_PREP_ARCSINH || cofactor > 0.0, "meld_prep_gene_moments: cofactor=%g must be positive", cofactor);
+  MELD_CHECK_ARG(ddof == 0 || ddof == 1, "meld_prep_gene_moments: ddof=%d outside {0, 1}", ddof);
+  MELD_CHECK_ARG(n_kept >= 1 && n_kept <= n_cells, "meld_prep_gene_moments: n_kept=%lld outside [1, n_cells=%lld]", (long long)n_kept,
+                 (long long)n_cells);
+  MELD_CHECK_ARG(n_kept - ddof >= 1, "meld_prep_gene_moments: n_kept=%lld leaves no degree of freedom with ddof=%d", (long long)n_kept, ddof);
+  const long long* rp = reinterpret_cast<const long long*>(rowptr);
+  const MomOperand a{col, val, (int)n_cells, row_keep, row_scale, rescale, transform, cofactor};
+  const unsigned grid = (unsigned)ceil_div(n_genes, MOM_WAVES);
+  if (val_f32)
+    gene_moments_kernel<true><<<grid, MOM_THREADS, 0, S(stream)>>>(rp, a, n_genes, gene_mask, n_kept, ddof, count, mean, var);
+  else
+    gene_moments_kernel<false><<<grid, MOM_THREADS, 0, S(stream)>>>(rp, a, n_genes, gene_mask, n_kept, ddof, count, mean, var);
+  MELD_LAUNCH_CHECK("gene_moments_kernel");
   return MELD_OK;
 }

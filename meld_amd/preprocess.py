@@ -11,6 +11,8 @@ densified and nothing but per-cell and per-gene vectors comes back to the host.
 * filters: ``filter_library_size``, ``filter_gene_set_expression``, ``filter_rare_genes``, ``filter_empty_cells``,
   ``filter_empty_genes`` -> ``(DeviceCSR, kept_indices)``; the indices stand in for scprep's ``*extra_data``: ``labels[kept]``;
 * ``library_size_normalize``, ``sqrt``, ``log``, ``arcsinh``;
+* per-gene moments and selection: ``gene_mean``, ``gene_variance``, ``gene_variability``, ``highly_variable_genes`` (one launch on the
+  gene-major copy ``DeviceCSR.T``; ``gene_moments_device`` returns the tensors, ``variability_from_moments`` is the host rule);
 * ``run``: the notebooks' sequence fused -- three statistics passes over the input and ONE rewrite; the transformed matrix for the
   SVD and the normalised one for ``rank_sum_test`` share their structure.  Bit for bit the result of the single functions called
   one after another.
@@ -30,7 +32,8 @@ import numpy as np
 __all__ = ["TRANSFORMS", "library_size", "library_size_device", "gene_capture_count", "gene_capture_count_device",
            "gene_set_expression", "gene_set_expression_device", "filter_library_size", "filter_gene_set_expression",
            "filter_rare_genes", "filter_empty_cells", "filter_empty_genes", "library_size_normalize", "sqrt", "log", "arcsinh",
-           "select", "run"]
+           "select", "run", "gene_moments_device", "gene_mean", "gene_variance", "variability_from_moments", "gene_variability",
+           "highly_variable_genes"]
 
 # the transform codes of include/meld_hip.h (MELD_PREP_*)
 TRANSFORMS = {None: 0, "identity": 0, "sqrt": 1, "log": 2, "log2": 3, "log10": 4, "arcsinh": 5}
@@ -409,9 +412,214 @@ def arcsinh(X, cofactor=5):
     return select(as_device_csr(X), transform="arcsinh", cofactor=cofactor)
 
 
+# ---- per-gene moments and highly variable genes ---------------------------------------------------------------------------------------------
+def _check_ddof(name, ddof):
+    if isinstance(ddof, bool) or ddof not in (0, 1):
+        raise ValueError("{}: expected ddof in [0, 1], got {!r}".format(name, ddof))
+    return int(ddof)
+
+
+def _check_kernel(name, kernel_size, smooth):
+    """``kernel_size``: an odd integer >= 1 (genes) or a fraction in (0, 1] of the genes; ``smooth``: an integer >= 0."""
+    if isinstance(kernel_size, bool) or not isinstance(kernel_size, numbers.Real):
+        raise ValueError("{}: expected `kernel_size` an odd integer or a fraction of the genes, got {!r}".format(name, kernel_size))
+    if isinstance(kernel_size, numbers.Integral):
+        if kernel_size < 1 or kernel_size % 2 == 0:
+            raise ValueError("{}: an integer `kernel_size` must be odd and at least 1, got {!r}".format(name, kernel_size))
+    elif not 0.0 < kernel_size <= 1.0:
+        raise ValueError("{}: a fractional `kernel_size` must lie in (0, 1], got {!r}".format(name, kernel_size))
+    if isinstance(smooth, bool) or not isinstance(smooth, numbers.Integral) or smooth < 0:
+        raise ValueError("{}: expected `smooth` an integer >= 0, got {!r}".format(name, smooth))
+
+
+def _check_n_top(name, n_top_genes, G=None):
+    if isinstance(n_top_genes, bool) or not isinstance(n_top_genes, numbers.Integral) or n_top_genes < 1 or (G is not None and n_top_genes > G):
+        raise ValueError("{}: expected `n_top_genes` an integer in [1, {}], got {!r}".format(name, "G" if G is None else G, n_top_genes))
+    return int(n_top_genes)
+
+
+def _hvg_rule(name, cutoff, percentile, n_top_genes, G=None):
+    """Exactly one of the three rules: ("cutoff" | "percentile", value, "above") as ``_cutoff_rule`` returns it, or ("n_top_genes", n)."""
+    given = [k for k, v in (("cutoff", cutoff), ("percentile", percentile), ("n_top_genes", n_top_genes)) if v is not None]
+    if len(given) != 1:
+        raise ValueError("{}: expected exactly one of `cutoff`, `percentile` and `n_top_genes`, got {}".format(name, given or "none"))
+    if n_top_genes is not None:
+        return ("n_top_genes", _check_n_top(name, n_top_genes, G))
+    if not isinstance(cutoff if cutoff is not None else percentile, numbers.Number):
+        raise ValueError("{}: expected a number for `{}`".format(name, given[0]))
+    return _cutoff_rule(name, cutoff, percentile, "above")
+
+
+def _hvg_keep(name, variability, rule):
+    """The rule on host variabilities: (bool mask, the cutoff used -- for ``n_top_genes`` the smallest variability kept)."""
+    if rule[0] == "n_top_genes":
+        n = _check_n_top(name, rule[1], variability.shape[0])
+        top = np.argsort(-variability, kind="stable")[:n]  # ties go to the lower gene index
+        mask = np.zeros(variability.shape[0], dtype=bool)
+        mask[top] = True
+        return mask, float(variability[top[-1]])
+    return _keep_mask(variability, *rule)
+
+
+def _input_genes(X):
+    """The number of genes where the input states it without the device (else None)."""
+    shape = getattr(X, "shape", None)
+    return int(shape[1]) if shape is not None and len(shape) == 2 else None
+
+
+def _moments(T, n_kept, row_keep=None, row_scale=None, rescale=1.0, code=0, cofactor=5.0, gene_mask=None, ddof=1):
+    """One launch of ``meld_prep_gene_moments`` on the gene-major ``DeviceCSR`` ``T`` [G, N]."""
+    import torch
+
+    from ._device_ops import stream
+    from ._lib import check, get_lib, ptr
+
+    G, N = T.shape
+    dev = T.device
+    if n_kept < 1 or n_kept - ddof < 1:
+        raise ValueError("gene_moments: {} kept cells leave nothing to average with ddof={}".format(n_kept, ddof))
+
+    def vector(x, dtype, n, what):
+        if x is None:
+            return None
+        x = (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))).to(device=dev, dtype=dtype).contiguous()
+        if x.dim() != 1 or int(x.shape[0]) != n:
+            raise ValueError("gene_moments: `{}` of shape {} for {} {}".format(what, tuple(x.shape), n, "cells" if n == N else "genes"))
+        return x
+
+    row_keep = vector(row_keep, torch.uint8, N, "row_keep")
+    row_scale = vector(row_scale, torch.float64, N, "row_scale")
+    gene_mask = vector(gene_mask, torch.uint8, G, "gene_mask")
+    count = torch.empty(G, dtype=torch.int32, device=dev)
+    mean = torch.empty(G, dtype=torch.float64, device=dev)
+    var = torch.empty(G, dtype=torch.float64, device=dev)
+    mat, hold = _arrays(T)
+    check(get_lib().meld_prep_gene_moments(*mat, ptr(row_keep), ptr(row_scale), float(rescale), code, float(cofactor), ptr(gene_mask),
+                                           int(n_kept), ddof, ptr(count), ptr(mean), ptr(var), stream()), "meld_prep_gene_moments")
+    del hold
+    return count, mean, var
+
+
+def _is_host_csc(X):
+    from . import sparse as _sp
+
+    if isinstance(X, _sp.DeviceCSR):
+        return False
+    inner = _sp._unwrap(X)
+    return bool(_sp._scipy_sparse().issparse(inner) and inner.format == "csc")
+
+
+def _gene_major(X):
+    """The gene-major copy of the input: ``as_device_csr(X).T`` (cached on a ``DeviceCSR``); the arrays of a host
+    ``scipy.sparse.csc_matrix`` ARE that copy and go up as they are (the route of meld_amd/diffexp.py)."""
+    if _is_host_csc(X):
+        from .diffexp import _gene_major as upload_csc
+
+        return upload_csc(X)
+    return as_device_csr(X).T
+
+
+def gene_moments_device(X, row_keep=None, row_scale=None, rescale=1.0, transform=None, cofactor=5.0, gene_mask=None, ddof=1):
+    """``(count, mean, var)`` of every gene over the kept cells: int32, fp64, fp64 device tensors [G], one launch of
+    ``meld_prep_gene_moments`` on the gene-major copy of ``X`` (``DeviceCSR.T``, transposed on first use and cached).
+
+    ``row_keep``: bool / uint8 [N] (None: every cell).  ``row_scale``: fp64 [N], with ``rescale``, ``transform`` and ``cofactor``
+    the value map of ``select``: the moments are those of ``f((v / row_scale[i]) * rescale)`` without that matrix being written.
+    ``gene_mask``: bool / uint8 [G], a gene outside it gets ``count = -1`` and zeros.  ``ddof``: 0 or 1.  ``count`` is the number of
+    stored entries in kept cells; the variance is a two-pass one, the implicit zeros included."""
+    import torch
+
+    code = _transform_code(transform)
+    ddof = _check_ddof("gene_moments", ddof)
+    if code == TRANSFORMS["arcsinh"] and not cofactor > 0:
+        raise ValueError("gene_moments: expected cofactor > 0, got {!r}".format(cofactor))
+    if isinstance(rescale, bool) or not isinstance(rescale, numbers.Real):
+        raise ValueError("gene_moments: expected a number for `rescale`, got {!r}".format(rescale))
+    T = _gene_major(X)
+    if row_keep is None:
+        n_kept = T.shape[1]
+    elif isinstance(row_keep, torch.Tensor):
+        n_kept = int((row_keep != 0).sum())
+    else:
+        n_kept = int(np.count_nonzero(np.asarray(row_keep)))
+    return _moments(T, n_kept, row_keep, row_scale, rescale, code, cofactor, gene_mask, ddof)
+
+
+def gene_mean(X):
+    """The mean of every gene over all cells: fp64 [G] on the host."""
+    return gene_moments_device(X, ddof=0)[1].cpu().numpy()
+
+
+def gene_variance(X, ddof=1):
+    """The variance of every gene over all cells (two passes, implicit zeros included): fp64 [G] on the host."""
+    ddof = _check_ddof("gene_variance", ddof)
+    return gene_moments_device(X, ddof=ddof)[2].cpu().numpy()
+
+
+def variability_from_moments(mean, var, kernel_size=0.005, smooth=5):
+    """The variability of genes from their means and variances: the variance minus the variance EXPECTED of a gene of that mean.
+
+    Restates ``scprep.measure.gene_variability`` from its documentation (a rolling median of the mean-variance curve, smoothed);
+    where scprep differs in a detail, THIS is the definition (tests/hvg_reference.py restates it):
+
+    * ``order``: the stable argsort of ``mean`` (ties: the lower gene index first);
+    * ``k``: ``kernel_size`` itself where it is an integer >= 1 (odd, else ValueError), else ``2 * (int(kernel_size * G) // 2) + 1``;
+    * expected variance: ``scipy.signal.medfilt(var[order], k)`` (zeros beyond the ends), then ``smooth`` passes of a three-point
+      mean ``((left + centre) + right) / 3`` with the end values replicated;
+    * variability: ``var - expected``, scattered back to gene order.
+
+    A host function on two fp64 arrays [G]; returns fp64 [G]."""
+    from scipy.signal import medfilt
+
+    _check_kernel("gene_variability", kernel_size, smooth)
+    mean = np.asarray(mean, dtype=np.float64)
+    var = np.asarray(var, dtype=np.float64)
+    if mean.ndim != 1 or mean.shape != var.shape or mean.shape[0] < 1:
+        raise ValueError("gene_variability: expected two vectors of one length, got shapes {} and {}".format(mean.shape, var.shape))
+    G = mean.shape[0]
+    k = int(kernel_size) if isinstance(kernel_size, numbers.Integral) else 2 * (int(kernel_size * G) // 2) + 1
+    order = np.argsort(mean, kind="stable")
+    expected = medfilt(var[order], k)
+    for _ in range(smooth):
+        padded = np.concatenate([expected[:1], expected, expected[-1:]])
+        expected = ((padded[:-2] + padded[1:-1]) + padded[2:]) / 3.0
+    out = np.empty(G, dtype=np.float64)
+    out[order] = var[order] - expected
+    return out
+
+
+def gene_variability(X, kernel_size=0.005, smooth=5, return_means=False):
+    """``scprep.measure.gene_variability`` as ``variability_from_moments`` defines it, from the device moments (``ddof=1``): fp64
+    [G] on the host, or ``(variability, means)``."""
+    _check_kernel("gene_variability", kernel_size, smooth)
+    _, mean, var = gene_moments_device(X)
+    mean = mean.cpu().numpy()
+    v = variability_from_moments(mean, var.cpu().numpy(), kernel_size, smooth)
+    return (v, mean) if return_means else v
+
+
+def highly_variable_genes(X, kernel_size=0.05, smooth=5, cutoff=None, percentile=80, n_top_genes=None):
+    """``scprep.select.highly_variable_genes``: keep the genes whose variability is above (``>``) ``cutoff``, above the
+    ``percentile`` of the variabilities, or the ``n_top_genes`` most variable ones (ties: the lower gene index).  Exactly one rule:
+    ``percentile=80`` is the default only while the other two are None.  Returns ``(DeviceCSR, kept)``.  The first call on a matrix
+    transposes it (cached as ``DeviceCSR.T``)."""
+    name = "highly_variable_genes"
+    _check_kernel(name, kernel_size, smooth)
+    if (cutoff is not None or n_top_genes is not None) and percentile == 80:
+        percentile = None
+    rule = _hvg_rule(name, cutoff, percentile, n_top_genes, _input_genes(X))
+    src = X if _is_host_csc(X) else as_device_csr(X)  # (one upload; a CSC input's own arrays serve the moments)
+    _, mean, var = gene_moments_device(src)
+    v = variability_from_moments(mean.cpu().numpy(), var.cpu().numpy(), kernel_size, smooth)
+    mask, _ = _hvg_keep(name, v, rule)
+    kept = _kept(name, mask, "gene")
+    return select(as_device_csr(src), cols=kept), kept
+
+
 # ---- the fused route ------------------------------------------------------------------------------------------------------------------------
 def run(X, min_library_size=None, max_library_size=None, library_size_percentile=None, min_cells=5, gene_cutoff=0, rescale=10000,
-        transform="sqrt", keep_normalized=True, cofactor=5):
+        transform="sqrt", keep_normalized=True, cofactor=5, hvg_percentile=None, hvg_cutoff=None, n_top_genes=None, hvg_kernel_size=0.05,
+        hvg_smooth=5):
     """The notebooks' sequence in one go: cells by library size, genes by capture count over the KEPT cells, library sizes over the
     KEPT genes, then one rewrite that selects, normalises and transforms.
 
@@ -419,6 +627,14 @@ def run(X, min_library_size=None, max_library_size=None, library_size_percentile
     ``library_size_percentile``: a number (keep above) or a pair (between) instead; none of them: every cell stays.  ``min_cells`` /
     ``gene_cutoff``: ``filter_rare_genes`` (``min_cells=None``: every gene stays).  ``rescale``: as ``library_size_normalize`` (None: no
     normalisation at all).  ``transform``: None, "sqrt", "log" (natural), "log2", "log10" or "arcsinh" (``cofactor``).
+
+    ``hvg_percentile`` / ``hvg_cutoff`` / ``n_top_genes`` (at most one; none: nothing below happens, no transposition, no further
+    launch): ``highly_variable_genes`` with ``hvg_kernel_size`` / ``hvg_smooth`` on the normalised and transformed values of the
+    kept cells, over the genes that passed ``min_cells`` -- one moments launch on the input's gene-major copy (``DeviceCSR.T``,
+    transposed on first use) between the library sizes and the rewrite, which then writes the selected genes only.  The cells are
+    still normalised by their library size over the genes of ``min_cells`` (normalise, then select), and ``library_size`` stays
+    over those; ``genes`` are the selected ones; ``info["hvg"]`` holds ``mean``, ``variance``, ``variability`` (host, over
+    ``info["hvg"]["genes"]``, the genes of ``min_cells``), the ``rule`` and the ``cutoff`` used.
 
     Returns a record: ``data`` (``DeviceCSR``, transformed), ``normalized`` (shares ``rowptr`` and ``col`` with ``data``; None unless
     ``keep_normalized``), ``cells`` / ``genes`` (host int64 indices into the input), ``library_size`` (kept cells over kept genes,
@@ -440,6 +656,10 @@ def run(X, min_library_size=None, max_library_size=None, library_size_percentile
         rule = _cutoff_rule("run", cutoffs[0], None, "above" if min_library_size is not None else "below")
     if transform == "arcsinh" and not cofactor > 0:
         raise ValueError("run: expected cofactor > 0, got {!r}".format(cofactor))
+    hvg = None
+    if hvg_percentile is not None or hvg_cutoff is not None or n_top_genes is not None:
+        _check_kernel("run (highly_variable_genes)", hvg_kernel_size, hvg_smooth)
+        hvg = _hvg_rule("run (highly_variable_genes)", hvg_cutoff, hvg_percentile, n_top_genes, _input_genes(X))
 
     A = as_device_csr(X)
     N, G = A.shape
@@ -468,9 +688,20 @@ def run(X, min_library_size=None, max_library_size=None, library_size_percentile
         scale = a[idx].contiguous()
         value = _rescale_value(rescale, libsize)
     info["rescale"] = value if rescale is not None else None
+    # 3 1/2. highly variable genes among the genes of step 2: the moments of the values the rewrite WOULD leave, from the input's
+    # gene-major copy (normalise, then select: the scales above stay those over the genes of step 2)
+    if hvg is not None:
+        name = "run (highly_variable_genes)"
+        _, mean, var = _moments(A.T, len(cells), row_keep, None if rescale is None else a, value, code, cofactor, col_mask, 1)
+        passed = torch.from_numpy(genes).to(dev)
+        mean, var = mean[passed].cpu().numpy(), var[passed].cpu().numpy()
+        variability = variability_from_moments(mean, var, hvg_kernel_size, hvg_smooth)
+        mask, cut = _hvg_keep(name, variability, hvg)
+        info["hvg"] = dict(mean=mean, variance=var, variability=variability, rule=hvg[0], cutoff=cut, genes=genes)
+        genes = genes[_kept(name, mask, "gene")]
     # 4. one count + scan + fill
-    out = select(A, rows=None if rule is None else cells, cols=None if min_cells is None else genes, scale=scale, rescale=value,
-                 transform=transform, cofactor=cofactor, keep_normalized=keep_normalized)
+    out = select(A, rows=None if rule is None else cells, cols=None if min_cells is None and hvg is None else genes, scale=scale,
+                 rescale=value, transform=transform, cofactor=cofactor, keep_normalized=keep_normalized)
     data, normalized = out if keep_normalized else (out, None)
     info.update(shape_after=data.shape, nnz_after=data.nnz, transform=transform, transform_code=code)
     return SimpleNamespace(data=data, normalized=normalized, cells=cells, genes=genes, library_size=libsize, cell_index=data.cell_index,
